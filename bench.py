@@ -13,7 +13,11 @@ A "step" is the reference's own definition (trainer.py:233,260-264): process_bat
 + backward + optimizer.step on one pre-resident synthetic KITTI-shaped batch (BASELINE.json
 configs[1]: MD2 ResNet-18 encoder + DepthDecoder + pose nets, 640x192, batch 12 per GPU, frames
 [0,-1,1], 4 scales, fp32), bracketed by barrier + device synchronise; value = global images / max
-over ranks of the wall time.  Rank 0 prints ONE JSON line carrying, besides the contract keys:
+over ranks of the wall time; ms_per_step = that wall time / --steps.  A plain run sets up, warms up, times the --steps
+steps and prints rank 0's ONE JSON line.  `--dump-outputs DIR` then also writes the last timed step's outputs and losses
+as DIR/<name>.npy (dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared file
+for file.  Every configuration runs with learning rate 0 (build_trainer in run_workload): the optimizer's kernels run, the
+weights stay at their seeded values, so the outputs are the same in every run.  With `--full` the line also carries:
 
   roofline      the hot path's most expensive HIP kernel inside the timed steps: algorithmic bytes
                 per launch (SURVEY.md 8d byte model) / its mean HIP-event duration, vs 8 TB/s HBM
@@ -22,6 +26,9 @@ over ranks of the wall time.  Rank 0 prints ONE JSON line carrying, besides the 
                 configs[0]: batch 4) timed on this box's host cores, bounded to a few steps
   hot_path_ab   BASELINE configs[1] A/B on this GPU: the hot path alone as fused HIP kernels vs the
                 same arithmetic as eager PyTorch-ROCm ops (grid_sample / avg_pool2d / cat / min)
+  secondary     one-GPU md2 runs: BASELINE configs[2] and [4] and the fresh-ordering / loader-fed lines, each timed in
+                this process with a fresh Trainer
+(With --step-graph off the kernels are timed inside the timed steps, so a plain run reports roofline and kernels too.)
 """
 import argparse
 import json
@@ -337,9 +344,59 @@ def batch_for(config, batch, rank):
     return draw.choices(range(0, 3), [.062, .573, .366], k=batch)     # epoch 5: P(m = 0,1,2) = .062 .573 .366
 
 
-def run_workload(args, ctx, config, steps, warmup, want_graph, dp_mode):
-    """Build a fresh Trainer for `config`, warm up, time EXACTLY `steps` steps between barrier + synchronise, then the
-    per-kernel HIP-event pass.  Returns a dict (trainer / opt / inputs included: the caller releases them)."""
+DUMP_BYTES = 64 << 20       # --dump-outputs: all files together
+DUMP_SAMPLE = 1 << 18       # elements kept of a larger array (a fixed, seeded sample of its flattened elements)
+
+
+def _dump_name(prefix, key):
+    import re
+    part = "_".join(str(p) for p in key) if isinstance(key, tuple) else str(key)
+    return prefix + "." + re.sub(r"[^A-Za-z0-9_.\-]", "_", part)
+
+
+def dump_outputs(directory, result):
+    """--dump-outputs: what a caller of the timed path receives from its last step - `Trainer.train_step`'s (outputs,
+    losses) - as DIR/<name>.npy, one file per tensor in name order ("loss.<key>", "out.<key>"), float32 (float64 for float64
+    and integer tensors).  An array of more than DUMP_SAMPLE elements is written as the elements at DUMP_SAMPLE sorted indices
+    drawn without replacement by numpy's generator seeded with 0 (the same indices in every run and every build); arrays
+    that would take the files past DUMP_BYTES are left out and named in the returned summary."""
+    import numpy as np
+    outputs, losses = result
+    named = {}
+    for prefix, d in (("loss", losses or {}), ("out", outputs or {})):
+        for k, v in d.items():
+            if torch.is_tensor(v):
+                name = _dump_name(prefix, k)
+                assert name not in named, "two outputs map to the file name %s" % name
+                named[name] = v
+    os.makedirs(directory, exist_ok=True)
+    total, sampled, omitted, files = 0, [], [], 0
+    for name in sorted(named):
+        v = named[name].detach()
+        dtype = np.float64 if (v.dtype == torch.float64 or not v.is_floating_point()) else np.float32
+        n = v.numel()
+        k = min(n, DUMP_SAMPLE)
+        if total + k * np.dtype(dtype).itemsize > DUMP_BYTES:
+            omitted.append(name)
+            continue
+        flat = v.reshape(-1)
+        if k < n:
+            idx = np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+            arr = flat[torch.from_numpy(idx).to(flat.device)].cpu().double().numpy().astype(dtype)
+            sampled.append(name)
+        else:
+            arr = v.cpu().double().numpy().astype(dtype)
+        np.save(os.path.join(directory, name + ".npy"), arr)
+        total += arr.nbytes
+        files += 1
+    return {"dir": directory, "files": files, "bytes": total, "sampled": sampled, "omitted": omitted}
+
+
+def run_workload(args, ctx, config, steps, warmup, want_graph, dp_mode, dump=None):
+    """Build a fresh Trainer for `config`, warm up, time EXACTLY `steps` steps between barrier + synchronise, write the
+    last step's outputs to `dump` (a directory, rank 0) if given, then - with --full - the per-kernel HIP-event pass of a
+    graph-replayed step and the live-candidate count.  Returns a dict (trainer / opt / inputs included: the caller releases
+    them)."""
     from baseboostdepth_amd import distributed as bdist
     from baseboostdepth_amd import ops
     from baseboostdepth_amd.synthetic import synthetic_batch
@@ -360,6 +417,12 @@ def run_workload(args, ctx, config, steps, warmup, want_graph, dp_mode):
             for m in tr.models.values():
                 m.to(memory_format=torch.channels_last)
         tr.set_train()
+        # learning rate 0: the optimizer runs the same kernels, but the weights stay at their seeded values, so every step
+        # computes the same outputs from the same inputs.  (MIOpen's convolution gradients accumulate with atomics and
+        # differ in the last bits from run to run; Adam would turn that into different weights, and outputs, after a few
+        # steps.  Its deterministic solvers cost 11x the step time and still are not bit-stable here.)
+        for g in tr.model_optimizer.param_groups:
+            g["lr"] = 0.0
         bdist.attach(tr)
         return tr, opt
 
@@ -371,12 +434,10 @@ def run_workload(args, ctx, config, steps, warmup, want_graph, dp_mode):
     if coherent:
         # the regime a TRAINED network produces (coherent arg-min maps, a few live candidates per tile) - constructed:
         # a planar scene whose frames are true shifts, networks whose heads predict exactly that scene
-        # (synthetic.structured_batch / constant_heads).  Learning rate 0: the optimizer runs the same kernels, the
-        # constructed registration does not drift over the timed steps
+        # (synthetic.structured_batch / constant_heads); learning rate 0 (build_trainer): the constructed registration does
+        # not drift over the timed steps
         from baseboostdepth_amd.synthetic import constant_heads, structured_batch
         constant_heads(trainer)
-        for g in trainer.model_optimizer.param_groups:
-            g["lr"] = 0.0
         inputs = structured_batch(ms, H, W, opt.scales, device=dev, seed=42 + rank)
     else:
         inputs = synthetic_batch(ms, H, W, opt.scales, device=dev, seed=42 + rank)
@@ -424,20 +485,25 @@ def run_workload(args, ctx, config, steps, warmup, want_graph, dp_mode):
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
     sync_all()
     t0 = time.perf_counter()
+    last = None
     for i in range(steps):
         marks[i].record()
-        trainer.train_step(inputs)
+        last = trainer.train_step(inputs)
     marks[steps].record()
     sync_all()
     elapsed = time.perf_counter() - t0
     backend.timer = None
+    dumped = dump_outputs(dump, last) if (dump and rank == 0) else None
+    del last
     exchange_ms, reduce_op, overlapped = 0.0, None, None
     if trainer.grad_sync is not None:
         trainer.grad_sync.timing = False
         exchange_ms, reduce_op = trainer.grad_sync.exchange_ms(), trainer.grad_sync.reduce_op
         overlapped = getattr(trainer.grad_sync, "launched_in_backward", None)
     kernel_timing = "HIP events around each C-ABI launch inside the timed steps"
-    if trainer.use_graph:
+    if trainer.use_graph and not args.full:
+        kernel_timing = "not measured (the timed region replays one hipGraph per step; --full times the kernels over eager steps)"
+    elif trainer.use_graph:
         # a replayed graph's nodes cannot be bracketed by events: the SAME kernels on the same inputs are timed over
         # eager steps of the same trainer right after the timed region (rocprofv3 stats under profiles/ agree)
         n_evt = max(5, min(steps, 20))
@@ -461,7 +527,7 @@ def run_workload(args, ctx, config, steps, warmup, want_graph, dp_mode):
         elapsed, median_ms, exchange_ms = float(t[0].item()), float(t[1].item()), float(t[2].item())
     S = len(opt.scales)
     live = None
-    if config.startswith("boosted") or config.startswith("trimin"):
+    if args.full and (config.startswith("boosted") or config.startswith("trimin")):
         # how many candidates win at least one pixel of a backward tile (32x16): what the backward's candidate loop sees
         from baseboostdepth_amd.synthetic import live_candidates_per_tile
         with torch.no_grad():
@@ -474,7 +540,7 @@ def run_workload(args, ctx, config, steps, warmup, want_graph, dp_mode):
             "elapsed": elapsed, "median_ms": median_ms, "rank_ms": rank_ms, "kernels": kernels, "dominant": dom, "roofline": roofline,
             "constants": cc, "graph_note": graph_note, "kernel_timing": kernel_timing, "exchange_ms": exchange_ms,
             "reduce_op": reduce_op, "overlapped": overlapped, "dp_mode": dp, "live_candidates_per_tile": live,
-            "value": args.batch * world * steps / elapsed, "ms_per_step": elapsed / steps * 1e3}
+            "dumped": dumped, "value": args.batch * world * steps / elapsed, "ms_per_step": elapsed / steps * 1e3}
 
 
 def release(res):
@@ -531,8 +597,18 @@ def main(argv=None):
                     help="`--gpus N` self-launch: seconds after which the child process group is terminated (status 124)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="only prove that --gpus N ranks start and rendezvous (one all-reduce), then exit")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else the benchmark measures: per-kernel HIP-event times and the "
+                         "roofline of a graph-replayed step (eager steps of their own), the stream-copy ceiling, the eager "
+                         "PyTorch-ROCm A/B, the `secondary` configurations and the CPU baseline.  Off: set up, warm up, time "
+                         "--steps steps, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned (Trainer.train_step's outputs and losses) "
+                         "as DIR/<name>.npy, float32/float64, at most 64 MB in all (larger arrays as a fixed seeded sample)")
     argv = list(sys.argv[1:] if argv is None else argv)
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # ---- multi-rank launch: before ANY GPU call (torch.cuda.* initialises HIP; a process that has done so
     #      must never be replaced, and the children must find the devices untouched)
@@ -578,7 +654,7 @@ def main(argv=None):
         r = run_fresh(args, ctx, args.config, want_graph) if args.config.endswith("_fresh") else run_loader_fed(args, ctx, want_graph)
         print(json.dumps(r))
         return 0
-    res = run_workload(args, ctx, args.config, args.steps, args.warmup, want_graph, head_mode)
+    res = run_workload(args, ctx, args.config, args.steps, args.warmup, want_graph, head_mode, dump=args.dump_outputs)
     trainer, opt, inputs = res["trainer"], res["opt"], res["inputs"]
 
     line = None
@@ -632,8 +708,11 @@ def main(argv=None):
                            (("one graph per step, bucketed RCCL all-reduces captured inside" if trainer.dp_capture else
                              "split: forward+backward+pack graph | eager all-reduce | optimizer graph")
                             if (trainer.use_graph and world > 1) else bool(trainer.use_graph))),
+            "full": bool(args.full),
         }
-        if roofline is not None:
+        if res["dumped"] is not None:
+            line["dump_outputs"] = res["dumped"]
+        if roofline is not None and args.full:
             # the on-box stream-copy ceiling beside the 8 TB/s specification (outside the timed region, < 1 s)
             try:
                 copy = stream_copy_ceiling(dev)
@@ -642,7 +721,7 @@ def main(argv=None):
                 roofline["peak_measured_how"] = copy
             except Exception as e:    # informational
                 roofline["peak_measured"] = "n/a (%s)" % type(e).__name__
-        if world == 1 and not args.no_eager_ab and args.config == "md2":
+        if args.full and world == 1 and not args.no_eager_ab and args.config == "md2":
             line["hot_path_ab"] = eager_hot_path_ab(trainer, inputs, opt)
             try:
                 line["eager_step"] = eager_full_step(trainer, inputs, opt)
@@ -654,7 +733,7 @@ def main(argv=None):
 
     # ---- BASELINE configs[2] and configs[4] in the same command (one GPU, default flags): fresh Trainer each, graphs
     #      released in between, never a re-exec
-    if world == 1 and args.config == "md2" and not args.no_secondary:
+    if args.full and world == 1 and args.config == "md2" and not args.no_secondary:
         secondary, t_sec = [], time.perf_counter()
         frozen, frozen_rows = {"md2": res["value"]}, {}
         for cfg in ("boosted", "boosted15", "boosted15_coherent", "trimin5", "vit", "boosted15_fresh", "trimin5_fresh", "md2_loader"):
@@ -752,7 +831,7 @@ def main(argv=None):
                     line["dp_modes"][mode] = entry
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
             line["cpu_baseline"]["cpu_model"] = cpu_model()
         print(json.dumps(line))

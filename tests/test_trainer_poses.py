@@ -1,5 +1,6 @@
 """CPU tier: Trainer.predict_poses (three pose modes), the network heads, and the whole
 process_batch-style chain against golden vectors from the reference (host-port backend)."""
+import json
 import os
 
 import numpy as np
@@ -79,46 +80,35 @@ def test_transformation_from_parameters_matches_golden():
 
 
 def test_custom_collate_matches_reference():
-    """Same keys, shapes and values as the reference's Trainer.custom_collate on ragged items."""
-    import refshim
-    if not refshim.reference_available():
-        pytest.skip("reference tree not present on this machine")
+    """Same keys, shapes and values as the reference's Trainer.custom_collate on ragged items (its results recorded in
+    tests/golden/collate_metrics.npz by tools/make_golden_collate.py: dtype, shape and a digest of every tensor's bits)."""
     import types
-    from make_golden import make_item, make_ref_trainer, make_opt as ref_opt
+    from make_golden_collate import COLLATE_CASES, collate_items, collate_record, load_collate
     from baseboostdepth_amd.trainer import Trainer
-    rt, rl, rn = refshim.import_reference()
-    for ms in ([3, 1, 0, 5], [0, 0], [7, 2], [1, 1, 1]):
-        gen = torch.Generator().manual_seed(1)
-        items = [make_item(gen, m, 32, 64, [0, 1, 2, 3], max(max(ms), 1), 0.3) for m in ms]
-        ref = make_ref_trainer(rt, rl, ref_opt(32, 64, len(ms), [0, 1, 2, 3], True, True)).custom_collate(items)
+    z = np.load(os.path.join(GOLDEN_DIR, "collate_metrics.npz"))
+    for i, ms in enumerate(COLLATE_CASES):
+        want_ms, want_tensors, want_lists = load_collate(z, i)
+        assert want_ms == list(ms)
         mine = Trainer.__new__(Trainer)
         mine.opt = types.SimpleNamespace(scales=[0, 1, 2, 3])
-        got = mine.custom_collate(items)
-        assert set(got.keys()) == set(ref.keys())
-        for k in ref:
-            if torch.is_tensor(ref[k]):
-                assert torch.equal(got[k], ref[k]), k
-            else:
-                assert got[k] == ref[k], k
+        got_tensors, got_lists = collate_record(mine.custom_collate(collate_items(ms)))
+        assert [r[0] for r in got_tensors] == [r[0] for r in want_tensors], ms
+        for g, w in zip(got_tensors, want_tensors):
+            assert g == w, (ms, g, w)
+        # (JSON spells the frame ids as the reference's lists do: ints and "s")
+        assert json.loads(json.dumps(got_lists)) == want_lists, ms
 
 
 def test_depth_metrics_oracle_matches_live_reference():
-    """Validation metrics (resize, Garg crop, median scaling, 7 errors): oracle vs the live reference
-    (the device kernel is checked against the same oracle and vectors in test_gpu_eval.py)."""
-    import refshim
-    if not refshim.reference_available():
-        pytest.skip("reference tree not present on this machine")
+    """Validation metrics (resize, Garg crop, median scaling, 7 errors): oracle vs the reference's
+    Trainer.compute_depth_losses on the same seeded inputs (its results recorded in tests/golden/collate_metrics.npz by
+    tools/make_golden_collate.py; the device kernel is checked against the same oracle and vectors in test_gpu_eval.py)."""
+    from make_golden_collate import METRIC_NAMES, metric_inputs
     from oracle import eval_ref
-    rt, rl, rn = refshim.import_reference()
-    gen = torch.Generator().manual_seed(2)
-    gt = (torch.rand(375, 1242, generator=gen) * 90).numpy()
-    gt[gt < 20] = 0                                              # sparse LiDAR-like ground truth
-    depth = 0.5 + 60 * torch.rand(1, 1, 192, 640, generator=gen)
-    names = ["de/abs_rel", "de/sq_rel", "de/rms", "de/log_rms", "da/a1", "da/a2", "da/a3"]
-    ref = rt.Trainer.__new__(rt.Trainer)
-    ref.device, ref.depth_metric_names, ref.gt_depths = torch.device("cpu"), names, [gt]
-    want = {}
-    ref.compute_depth_losses({("depth", 0, 0): depth.clone()}, want, 0)
+    z = np.load(os.path.join(GOLDEN_DIR, "collate_metrics.npz"))
+    assert list(z["metrics/names"]) == METRIC_NAMES
+    depth, gt = metric_inputs()
     got = eval_ref.compute_depth_losses_ref(depth.clone(), gt)["metrics"]
-    for i, k in enumerate(names):
-        assert abs(got[i] - float(want[k])) < 1e-6 * max(1.0, abs(float(want[k]))), (k, got[i], want[k])
+    for i, k in enumerate(METRIC_NAMES):
+        want = float(z["metrics/want"][i])
+        assert abs(got[i] - want) < 1e-6 * max(1.0, abs(want)), (k, got[i], want)
