@@ -1,0 +1,215 @@
+"""Single-image depth prediction (the reference's test_simple.py) on the device.
+
+`DepthPredictor.predict` takes uint8 RGB images of any sizes and returns, per image, the magma-coloured disparity at
+the image's own size - what test_simple.py writes as `<name>_Base.jpg`.  A batch costs one upload, the Pillow-exact
+LANCZOS resize + ToTensor kernels (`imageops.ImagePipeline`), the networks, one `bbd_disp_viz` call (upsampling,
+percentile, normalisation and colour map without leaving the device) and one copy of the colours back; the
+reference does all of that per image on the host with Pillow, numpy and matplotlib (test_simple.py:124-148).
+
+`run_cli` is the command line of the repository's root `test_simple.py`.
+"""
+import argparse
+import glob
+import os
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+from . import imageops, ops
+
+HOST_THREADS = 8          # decode / save pool; a fixed small number, never the machine's CPU count
+
+
+class DepthPrediction:
+    """Result of one image: `color` uint8 [H,W,3], `vmin`/`vmax` the normalisation range of the scaled disparity,
+    and - when asked for - `scaled_disp` fp32 [H,W] and `depth` = 1 / scaled_disp."""
+
+    __slots__ = ("color", "vmin", "vmax", "scaled_disp", "depth")
+
+    def __init__(self, color, vmin, vmax, scaled_disp=None):
+        self.color, self.vmin, self.vmax, self.scaled_disp = color, float(vmin), float(vmax), scaled_disp
+        self.depth = None if scaled_disp is None else np.float32(1) / scaled_disp
+
+
+class DepthPredictor:
+    def __init__(self, encoder, decoder, feed_height, feed_width, device="cuda:0", min_depth=0.1, max_depth=80.0,
+                 batch_size=16, backend=None):
+        self.device = torch.device(device)
+        self.encoder = encoder.to(self.device).eval()
+        self.decoder = decoder.to(self.device).eval()
+        self.feed_height, self.feed_width = int(feed_height), int(feed_width)
+        self.min_depth, self.max_depth = float(min_depth), float(max_depth)
+        self.batch_size = int(batch_size)
+        self.backend = backend or ops.default_backend()
+        self.pipe = imageops.ImagePipeline(self.device, self.backend)
+        self.last_disp = None
+
+    @classmethod
+    def from_weights(cls, folder, vit=False, num_layers=18, device="cuda:0", **kw):
+        """Loads `encoder.pth` / `depth.pth` of a weights folder as evaluation.evaluate and the reference do
+        (test_simple.py:52-93): the feed size is stored inside encoder.pth, foreign keys are filtered out."""
+        from . import networks, tuning
+        tuning.use_shipped_db()
+        folder = os.path.expanduser(folder)
+        assert os.path.isdir(folder), "Cannot find a folder at {}".format(folder)
+        enc_dict = torch.load(os.path.join(folder, "encoder.pth"), map_location=device)
+        height, width = enc_dict["height"], enc_dict["width"]
+        if vit:
+            from . import networksvit
+            encoder = networksvit.mpvit_small(checkpoint=None)
+            encoder.num_ch_enc = [64, 128, 216, 288, 288]
+            decoder = networksvit.DepthDecoder()
+        else:
+            encoder = networks.ResnetEncoder(num_layers, False)
+            decoder = networks.DepthDecoder(encoder.num_ch_enc)
+        own = encoder.state_dict()
+        encoder.load_state_dict({k: v for k, v in enc_dict.items() if k in own})
+        decoder.load_state_dict(torch.load(os.path.join(folder, "depth.pth"), map_location=device), strict=False)
+        return cls(encoder, decoder, height, width, device, **kw)
+
+    def prepare(self, images):
+        """uint8 HWC RGB arrays of any sizes -> fp32 [n,3,feed_h,feed_w] on the device, bit-equal to
+        `ToTensor()(pil.resize((feed_w, feed_h), LANCZOS))` of each: one upload, then the image kernels."""
+        arrays = [np.ascontiguousarray(im) for im in images]
+        jobs, off = [], 0
+        for a in arrays:
+            assert a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 3, "images are HWC uint8 RGB"
+            jobs.append((off, a.shape[0], a.shape[1], False))
+            off += a.size
+        host = torch.empty(off, dtype=torch.uint8, pin_memory=self.device.type == "cuda")
+        flat = host.numpy()
+        for a, (o, _, _, _) in zip(arrays, jobs):
+            flat[o:o + a.size] = a.reshape(-1)
+        src = host.to(self.device, non_blocking=True)
+        n = len(arrays)
+        u8 = self.pipe.resize(src, jobs, self.feed_height, self.feed_width)
+        x = torch.empty(n, 3, self.feed_height, self.feed_width, dtype=torch.float32, device=self.device)
+        self.pipe.to_float(u8, list(range(n)), x, list(range(n)))
+        self.pipe.flush()
+        return x
+
+    def disparity(self, x):
+        """Network output ("disp", 0) for prepared inputs, in batches of at most `batch_size`.  Convolutions are asked
+        for deterministic algorithms: without that, MIOpen may pick solvers whose sums land in a different order from
+        run to run, the disparity moves by an ulp here and there, and now and then a pixel changes its colour bin - the
+        same picture would not always give the same file."""
+        cudnn = torch.backends.cudnn
+        outs, was = [], cudnn.deterministic
+        cudnn.deterministic = True
+        try:
+            for first in range(0, x.shape[0], self.batch_size):
+                outs.append(self.decoder(self.encoder(x[first:first + self.batch_size]))[("disp", 0)])
+        finally:
+            cudnn.deterministic = was
+        return outs[0] if len(outs) == 1 else torch.cat(outs)
+
+    def predict(self, images, want_float=False):
+        if not len(images):
+            return []
+        sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
+        with torch.no_grad():
+            self.encoder.eval()
+            self.decoder.eval()
+            disp = self.last_disp = self.disparity(self.prepare(images))      # kept for inspection (tests)
+            colour, floats, stats = ops.disp_viz(disp, sizes, self.min_depth, self.max_depth, 95.0, want_float,
+                                                 self.backend)
+            buffers = [ops.viz_buffer(colour), stats] + ([ops.viz_buffer(floats)] if want_float else [])
+            host = [_to_host(b) for b in buffers]
+            if self.device.type == "cuda":
+                torch.cuda.current_stream(self.device).synchronize()
+        col_h, stats_h = host[0].numpy(), host[1].numpy()
+        flt_h = host[2].numpy() if want_float else None
+        results, off = [], 0
+        for i, (H0, W0) in enumerate(sizes):
+            npx = H0 * W0
+            col = col_h[3 * off:3 * (off + npx)].reshape(H0, W0, 3)
+            sd = flt_h[off:off + npx].reshape(H0, W0) if want_float else None
+            results.append(DepthPrediction(col, stats_h[i, 0], stats_h[i, 1], sd))
+            off += ops.viz_granule(npx)
+        return results
+
+
+def _to_host(t):
+    if not t.is_cuda:
+        return t
+    host = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+    host.copy_(t, non_blocking=True)
+    return host
+
+
+# ---------------------------------------------------------------------------- command line (test_simple.py)
+def parse_args(argv=None):
+    parser = argparse.ArgumentParser(description="Predict depth for one image or a folder of images and save the "
+                                                 "colour-mapped disparity as <name>_Base.jpg.")
+    parser.add_argument("--image_path", type=str, required=True, help="path to a test image or folder of images")
+    parser.add_argument("--save_path", type=str, required=True,
+                        help="output folder for a folder of images (created); a single image is written next to itself")
+    parser.add_argument("--ext", type=str, default="jpg", help="image extension to search for in a folder")
+    parser.add_argument("--vit", action="store_true", help="the weights are a MonoViT model")
+    parser.add_argument("--weights", type=str, required=True, help="folder holding encoder.pth and depth.pth")
+    parser.add_argument("--save_npy", action="store_true",
+                        help="also write <name>_disp.npy: the scaled disparity, float32, at the original size")
+    parser.add_argument("--batch_size", type=int, default=16, help="images per device batch")
+    parser.epilog = ("Inputs whose names end in _disp.jpg or _Base.jpg are skipped, so that a second run over a "
+                     "folder of jpg files does not colour its own outputs.")
+    return parser.parse_args(argv)
+
+
+def find_inputs(image_path, save_path, ext):
+    """(paths, output directory) by the reference's rules (test_simple.py:103-122) plus the _Base.jpg skip."""
+    if os.path.isfile(image_path):
+        paths, out_dir = [image_path], os.path.dirname(image_path)
+    elif os.path.isdir(image_path):
+        paths, out_dir = sorted(glob.glob(os.path.join(image_path, "*.{}".format(ext)))), save_path
+    else:
+        raise Exception("Can not find args.image_path: {}".format(image_path))
+    paths = [p for p in paths if not (p.endswith("_disp.jpg") or p.endswith("_Base.jpg"))]
+    return paths, out_dir
+
+
+def _load(path):
+    import PIL.Image as pil
+    with pil.open(path) as im:
+        return np.asarray(im.convert("RGB"))
+
+
+def _save(out_dir, path, result, save_npy):
+    import PIL.Image as pil
+    stem = os.path.splitext(os.path.basename(path))[0]
+    dest = os.path.join(out_dir, "{}_Base.jpg".format(stem))
+    pil.fromarray(result.color).save(dest)
+    if save_npy:
+        np.save(os.path.join(out_dir, "{}_disp.npy".format(stem)), result.scaled_disp)
+    return dest
+
+
+def run_cli(args, predictor=None):
+    """Body of test_simple.py.  `predictor` may be injected (tests); by default it is loaded from `args.weights`.
+    Returns the list of written JPEG paths."""
+    paths, out_dir = find_inputs(args.image_path, args.save_path, args.ext)
+    if predictor is None:
+        print("-> Loading model from ", args.weights)
+        predictor = DepthPredictor.from_weights(args.weights, vit=args.vit, batch_size=args.batch_size)
+    print("-> Predicting on {:d} test images".format(len(paths)))
+    if out_dir and not os.path.exists(out_dir):
+        os.makedirs(out_dir)
+    out_dir = out_dir or "."
+    batch = max(1, int(getattr(args, "batch_size", 16)))
+    written, pending = [], []
+    with ThreadPoolExecutor(max_workers=HOST_THREADS) as pool:
+        chunks = [paths[i:i + batch] for i in range(0, len(paths), batch)]
+        loads = [pool.map(_load, c) for c in chunks[:1]]                 # decode runs one batch ahead
+        for k, chunk in enumerate(chunks):
+            images = list(loads[k])
+            if k + 1 < len(chunks):
+                loads.append(pool.map(_load, chunks[k + 1]))
+            results = predictor.predict(images, want_float=args.save_npy)
+            pending += [pool.submit(_save, out_dir, p, r, args.save_npy) for p, r in zip(chunk, results)]
+        written = [f.result() for f in pending]
+    print("-> Done!")
+    return written
+
+
+def main(argv=None):
+    return run_cli(parse_args(argv))

@@ -1488,3 +1488,74 @@ class _DispConv(torch.autograd.Function):
 def dispconv(x, weight, bias, backend=None):
     """layers.Conv3x3(C, 1): reflection pad + 3x3 convolution to ONE channel + bias (the decoder's disparity heads)."""
     return _DispConv.apply(x, weight, bias, backend or default_backend())
+
+
+# ---------------------------------------------------------------------------- colour-mapped disparity
+_MAGMA = {}
+
+
+def magma_lut(device="cpu"):
+    """uint8 [256,3]: magma as matplotlib's `to_rgba(...)[..., :3] * 255 -> uint8` yields it.  Read from the shipped
+    table (magma_lut.hex, written by tools/make_magma_lut.py); matplotlib is never imported."""
+    key = str(device)
+    if key not in _MAGMA:
+        if "cpu" not in _MAGMA:
+            with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "magma_lut.hex")) as f:
+                rows = [line.strip() for line in f if line.strip()]
+            assert len(rows) == 256 and all(len(r) == 6 for r in rows)
+            _MAGMA["cpu"] = torch.tensor([[int(r[0:2], 16), int(r[2:4], 16), int(r[4:6], 16)] for r in rows],
+                                         dtype=torch.uint8)
+        _MAGMA[key] = _MAGMA["cpu"].to(device)
+    return _MAGMA[key]
+
+
+def viz_granule(npx):
+    """Pixels an image of `npx` pixels occupies in the buffers of `disp_viz`: 4-pixel granules, so that every image
+    starts on a 4-byte boundary of the colour buffer (packed stores)."""
+    return (npx + 3) // 4 * 4
+
+
+def viz_buffer(views):
+    """The one buffer the views returned by `disp_viz` point into (images `viz_granule` pixels apart)."""
+    return views[0]._base
+
+
+def disp_viz(disp, sizes, min_depth=0.1, max_depth=80.0, percentile=95.0, want_float=False, backend=None):
+    """test_simple.py:135-148 for a batch: network disparities `disp` [n,1,h,w] (sigmoid output) -> per image the
+    magma-coloured scaled disparity at its original size `sizes[i] = (H0, W0)` (ragged), normalised between its minimum
+    and its `percentile`-th percentile (np.percentile, exact).  One `bbd_disp_viz` call, no host synchronisation.
+
+    Returns (colour, floats, stats): `colour` a list of uint8 [H0,W0,3] views into ONE buffer (`colour[0]._base` - a
+    single copy brings all of them to the host), `floats` a list of fp32 [H0,W0] views of the scaled disparity (None
+    unless `want_float`), `stats` fp32 [n,4] = vmin, vmax and the two order statistics vmax was interpolated from."""
+    backend = backend or default_backend()
+    disp = disp.detach()
+    if disp.dim() == 4:
+        assert disp.shape[1] == 1
+        disp = disp[:, 0]
+    disp = disp.contiguous().float()
+    backend._check(disp)
+    n, h, w = disp.shape
+    assert len(sizes) == n and n > 0
+    dev = disp.device
+    rows, off = [], 0
+    for H0, W0 in sizes:
+        assert H0 >= 1 and W0 >= 1 and H0 * W0 < 2 ** 31
+        rows.append((off & 0x7FFFFFFF | (-(off >> 31 & 1) << 31), off >> 32, int(H0), int(W0)))
+        off += viz_granule(H0 * W0)
+    desc = torch.tensor(rows, dtype=torch.int32)
+    if dev.type == "cuda":
+        desc = desc.pin_memory().to(dev, non_blocking=True)
+    out = torch.empty(off * 3, dtype=torch.uint8, device=dev)
+    outf = torch.empty(off, dtype=torch.float32, device=dev) if want_float else None
+    stats = torch.empty(n, 4, dtype=torch.float32, device=dev)
+    scratch = torch.empty(backend.lib.disp_viz_scratch_ints(n), dtype=torch.int32, device=dev)
+    backend.run("bbd_disp_viz", disp, ptr(disp), ptr(desc), ptr(magma_lut(dev)), ptr(out), ptr(outf), ptr(stats),
+                ptr(scratch), n, h, w, 1.0 / max_depth, 1.0 / min_depth, float(percentile))
+    colour, floats = [], ([] if want_float else None)
+    for (lo, hi, H0, W0) in rows:
+        o = (lo & 0xFFFFFFFF) | (hi << 32)
+        colour.append(out[3 * o:3 * (o + H0 * W0)].view(H0, W0, 3))
+        if want_float:
+            floats.append(outf[o:o + H0 * W0].view(H0, W0))
+    return colour, floats, stats

@@ -34,8 +34,8 @@ extern "C" {
  * work-item table of the fused launches, per-row `invert` of the pose matrices, the multi-scale smoothness launches);
  * 6 = round 5: bbd_bn_act_grouped_fwd gained `untracked_groups` (the padding group of the batched pose pass);
  * 7 = round 6: bbd_bn_act_grouped_dev_fwd / _bwd (group table resident on the device: launches whose arguments do not
- * depend on the batch signature). */
-#define BBD_ABI_VERSION 7
+ * depend on the batch signature); 8 = bbd_disp_viz / bbd_disp_viz_scratch_ints (single-image prediction). */
+#define BBD_ABI_VERSION 8
 
 /* Source frames live in separate tensors, one per frame id (inputs[("color", f, 0)],
  * trainer.py:428).  A "slot" indexes a host array of their base pointers. */
@@ -292,6 +292,26 @@ int bbd_ssim_bwd(const float* x, const float* y, const float* grad_out, float* g
 int bbd_depth_metrics(const float* pred, const float* gt, const int32_t* desc, float* out, int n, int h,
                       int w, double min_depth, double max_depth, double clamp_lo, double clamp_hi,
                       double scale_factor, int flags, void* stream);
+
+/* Colour-mapped disparity of single-image prediction (test_simple.py:135-148), n images per call, never leaving
+ * the device.  For image i, with desc[i] = {offset_lo, offset_hi (pixels), H0, W0} (original sizes, ragged):
+ *   d    = F.interpolate(disp[i], (H0, W0), bilinear, align_corners=False)      (not materialised)
+ *   s    = min_disp + (max_disp - min_disp) * d                                 layers.disp_to_depth, fp32
+ *   vmin = min(s);  vmax = np.percentile(s, percentile)                         numpy "linear" method on float32:
+ *          both bracketing order statistics are selected exactly (radix select on the float bit patterns, integer
+ *          histograms) and interpolated in numpy's float32 arithmetic (bbd_viz_math.h)
+ *   out_u8[3*offset + 3*(y*W0+x) + c] = trunc(magma[idx][c] * 255),  idx = trunc((s - vmin) / (vmax - vmin) * 256),
+ *          256 and everything above vmax -> 255, vmax == vmin -> 0       matplotlib Normalize + ScalarMappable.to_rgba
+ * lut is that table, uint8 [256,3] (baseboostdepth_amd/magma_lut.hex).  out_float (may be NULL) receives s at
+ * out_float + offset.  stats[i] = {vmin, vmax, lower, upper order statistic}.  Offsets that are multiples of 4
+ * pixels get packed 12-byte stores.  scratch holds bbd_disp_viz_scratch_ints(n) int32 and is zeroed on `stream` by
+ * the call; four launches, no host synchronisation; results do not depend on launch geometry or atomic order.
+ * percentile in (0, 100]; min_disp = 1 / max_depth, max_disp = 1 / min_depth as Python doubles. */
+#define BBD_VIZ_DESC 4
+int bbd_disp_viz_scratch_ints(int n);
+int bbd_disp_viz(const float* disp, const int32_t* desc, const uint8_t* lut, uint8_t* out_u8, float* out_float,
+                 float* stats, int32_t* scratch, int n, int h, int w, double min_disp, double max_disp,
+                 double percentile, void* stream);
 
 /* ---- Loader image pipeline: replaces the per-item Pillow/torchvision work of
  * datasets/mono_dataset.py:186-205 (Resize(LANCZOS) chain, ColorJitter, ToTensor) and the stacking of
