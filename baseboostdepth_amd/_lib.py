@@ -20,7 +20,7 @@ PROJ_STRIDE = 24
 KIND_WARP, KIND_IDENT, FLAG_NO_POSE_GRAD = 0, 1, 0x100
 COMPOSE_STRIDE, COMPOSE_ERROR, COMPOSE_REPLACE = 12, 1, 2
 PAIR_SHIFT = 16        # bits 16-23 of bbd_cand_t.kind: 1 + index of the pass partner (hint), 0 = none
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _p = ctypes.c_void_p
 _i = ctypes.c_int
@@ -64,6 +64,8 @@ SIGNATURES = {
     "bbd_depth_metrics": [_p, _p, _p, _p, _i, _i, _i, _d, _d, _d, _d, _d, _i, _p],
     "bbd_disp_viz_scratch_ints": [_i],
     "bbd_disp_viz": [_p] * 7 + [_i, _i, _i, _d, _d, _d, _p],
+    "bbd_velo_depth_scratch_ints": [_i, _i],
+    "bbd_velo_depth": [_p, _p, _p, _p, _i, _p, _i, _i, _i, _p],
     "bbd_resample_h_u8": [_p, _p, _p, _i, _i, _p, _p, _i, _p],
     "bbd_resample_v_u8": [_p, _p, _p, _i, _i, _i, _p, _p, _i, _p],
     "bbd_color_jitter_u8": [_p, _p, _p, _i, _i, _i, _p, _p],
@@ -112,6 +114,7 @@ SIGNATURES = {
 RESAMPLE_JOB, RESAMPLE_FLIP, JITTER_JOB, CONVERT_JOB = 12, 1, 12, 4
 EVAL_DESC, EVAL_OUT = 8, 12
 VIZ_DESC = 4
+VELO_DESC, VELO_VEL_DEPTH = 8, 1
 EVAL_PRED_IS_DISP, EVAL_MEDIAN_MIDPOINT, EVAL_NO_MEDIAN_SCALING = 1, 2, 4
 
 
@@ -181,6 +184,9 @@ class HipLibrary:
 
     def disp_viz_scratch_ints(self, n):
         return self._dll.bbd_disp_viz_scratch_ints(n)
+
+    def velo_depth_scratch_ints(self, total_pixels, n_frames):
+        return self._dll.bbd_velo_depth_scratch_ints(total_pixels, n_frames)
 
     def dispconv_scratch_doubles(self, C):
         return self._dll.bbd_dispconv_scratch_doubles(C)

@@ -41,6 +41,26 @@ class GroundTruthSet:
         self.buffer = torch.from_numpy(flat).to(device)
         self.desc = torch.from_numpy(desc).to(device)
 
+    @classmethod
+    def from_packed(cls, buffer, shapes, crop=True):
+        """The set over maps that ALREADY lie back to back in the device buffer `buffer` (float32, map i of shape
+        `shapes[i]` after map i - 1), as `kitti_utils.generate_depth_maps` leaves them: only the descriptor table is
+        built and uploaded, the maps never visit the host."""
+        shapes = [(int(gh), int(gw)) for gh, gw in shapes]
+        assert buffer.dtype == torch.float32 and buffer.dim() == 1 and buffer.is_contiguous()
+        assert buffer.numel() == sum(gh * gw for gh, gw in shapes)
+        desc = np.zeros((len(shapes), EVAL_DESC), dtype=np.int32)
+        off = 0
+        for i, (gh, gw) in enumerate(shapes):
+            win = garg_window(gh, gw) if crop else (0, gh, 0, gw)
+            desc[i] = (off & 0xFFFFFFFF if off < 2 ** 31 else (off & 0xFFFFFFFF) - 2 ** 32, off >> 32, gh, gw) + win
+            off += gh * gw
+        self = cls.__new__(cls)
+        self.shapes = shapes
+        self.buffer = buffer
+        self.desc = torch.from_numpy(desc).to(buffer.device)
+        return self
+
     def __len__(self):
         return len(self.shapes)
 
@@ -81,7 +101,9 @@ def evaluate(opt, dataloader=None, gt_depths=None, models=None, batch_size=16):
 
     `dataloader` / `gt_depths` / `models` may be injected (tests, synthetic splits); by default they are
     built from `opt.splits_dir/<eval_split>/{test_files.txt, gt_depths.npz}`, `opt.kt_path` and
-    `opt.load_weights_folder`."""
+    `opt.load_weights_folder`.  Where `gt_depths.npz` does not exist (the reference ships none) and the split is `eigen`
+    or `eigen_zhou`, the ground truth is projected from the Velodyne scans under `opt.kt_path` on the device
+    (`kitti_utils.generate_depth_maps`: what `export_gt_depth.py` writes, without the file)."""
     from . import tuning
     tuning.use_shipped_db()      # (no Trainer is built here: the tuned MIOpen database is wired explicitly)
     import os
@@ -119,9 +141,16 @@ def evaluate(opt, dataloader=None, gt_depths=None, models=None, batch_size=16):
                                       naive_mix=True)
         dataloader = datasets.DeviceLoader(ds, batch_size, datasets.DeviceCollate(height, width, [0], device),
                                            shuffle=False, drop_last=False, num_workers=getattr(opt, "num_workers", 8))
+    gt_path = os.path.join(split_dir, "gt_depths.npz")
+    if gt_depths is None and not os.path.isfile(gt_path) and opt.eval_split in ("eigen", "eigen_zhou"):
+        # what export_gt_depth.py would have written, straight into the device buffer the metrics read
+        from . import kitti_utils
+        frames = kitti_utils.split_frames(split_dir, opt.eval_split, opt.kt_path)
+        print("-> %s not found: ground truth of %d frames projected from the Velodyne scans under %s on the device"
+              % (gt_path, len(frames), opt.kt_path))
+        gt_depths = kitti_utils.generate_depth_maps(frames, device, vel_depth=True)
     if gt_depths is None:
-        gt_depths = np.load(os.path.join(split_dir, "gt_depths.npz"), fix_imports=True, encoding="latin1",
-                            allow_pickle=True)["data"]
+        gt_depths = np.load(gt_path, fix_imports=True, encoding="latin1", allow_pickle=True)["data"]
     gts = gt_depths if isinstance(gt_depths, GroundTruthSet) else GroundTruthSet(gt_depths, device)
 
     median_scaling = not opt.disable_median_scaling

@@ -1559,3 +1559,50 @@ def disp_viz(disp, sizes, min_depth=0.1, max_depth=80.0, percentile=95.0, want_f
         if want_float:
             floats.append(outf[o:o + H0 * W0].view(H0, W0))
     return colour, floats, stats
+
+
+# ---------------------------------------------------------------------------- Velodyne depth maps
+def velo_depth(points, counts, proj, shapes, out=None, offsets=None, vel_depth=False, backend=None):
+    """kitti_utils.py:46-98 (generate_depth_map) for a ragged batch of frames in ONE `bbd_velo_depth` call: a memset
+    and two launches, no host synchronisation.
+
+    `points` fp32 [sum(counts), 4] holds the scans back to back as the .bin files store them (x, y, z, reflectance - the
+    last column is ignored), `proj` [n,3,4] float64 the projection matrices (`kitti_utils.velo_projection`), `shapes[i]
+    = (h, w)`.  Frame i is written to `out[offsets[i] : offsets[i] + h*w]`; without `out` a packed buffer is allocated
+    and frames follow one another.  Returns (out, offsets)."""
+    backend = backend or default_backend()
+    points = points.detach()
+    assert points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] == 4
+    points = points.contiguous()
+    n = len(counts)
+    assert n > 0 and len(shapes) == n and sum(counts) == points.shape[0]
+    dev = points.device
+    proj = torch.as_tensor(proj, dtype=torch.float64).reshape(n, 12).contiguous()
+    sizes = [int(h) * int(w) for h, w in shapes]
+    assert all(h >= 1 and w >= 1 for h, w in shapes) and all(c >= 0 for c in counts)
+    if out is None:
+        assert offsets is None
+        offsets = [0] * n
+        for i in range(1, n):
+            offsets[i] = offsets[i - 1] + sizes[i - 1]
+        out = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
+    assert len(offsets) == n and out.dtype == torch.float32 and out.is_contiguous() and out.device == dev
+    assert all(0 <= o and o + s <= out.numel() for o, s in zip(offsets, sizes))
+    backend._check(points, out)
+    rows, first_point, first_pixel = [], 0, 0
+    for (h, w), c, o, s in zip(shapes, counts, offsets, sizes):
+        rows.append((o & 0x7FFFFFFF | (-(o >> 31 & 1) << 31), o >> 32, int(h), int(w), int(c), first_point, first_pixel, 0))
+        first_point += int(c)
+        first_pixel += s
+    n_ints = backend.lib.velo_depth_scratch_ints(first_pixel, n)
+    if n_ints < 0:
+        raise _lib.BbdError("velo_depth: %d pixels in one call are more than the scratch contract holds; "
+                            "split the batch" % first_pixel)
+    desc = torch.tensor(rows, dtype=torch.int32)
+    if dev.type == "cuda":
+        desc = desc.pin_memory().to(dev, non_blocking=True)
+        proj = proj.pin_memory().to(dev, non_blocking=True)
+    scratch = torch.empty(n_ints, dtype=torch.int32, device=dev)
+    backend.run("bbd_velo_depth", out, ptr(points), ptr(desc), ptr(proj), ptr(scratch), n_ints, ptr(out), n,
+                int(max(counts)), _lib.VELO_VEL_DEPTH if vel_depth else 0)
+    return out, list(offsets)

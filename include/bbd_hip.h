@@ -34,8 +34,9 @@ extern "C" {
  * work-item table of the fused launches, per-row `invert` of the pose matrices, the multi-scale smoothness launches);
  * 6 = round 5: bbd_bn_act_grouped_fwd gained `untracked_groups` (the padding group of the batched pose pass);
  * 7 = round 6: bbd_bn_act_grouped_dev_fwd / _bwd (group table resident on the device: launches whose arguments do not
- * depend on the batch signature); 8 = bbd_disp_viz / bbd_disp_viz_scratch_ints (single-image prediction). */
-#define BBD_ABI_VERSION 8
+ * depend on the batch signature); 8 = bbd_disp_viz / bbd_disp_viz_scratch_ints (single-image prediction);
+ * 9 = bbd_velo_depth / bbd_velo_depth_scratch_ints (ground-truth depth maps from Velodyne scans). */
+#define BBD_ABI_VERSION 9
 
 /* Source frames live in separate tensors, one per frame id (inputs[("color", f, 0)],
  * trainer.py:428).  A "slot" indexes a host array of their base pointers. */
@@ -312,6 +313,30 @@ int bbd_disp_viz_scratch_ints(int n);
 int bbd_disp_viz(const float* disp, const int32_t* desc, const uint8_t* lut, uint8_t* out_u8, float* out_float,
                  float* stats, int32_t* scratch, int n, int h, int w, double min_disp, double max_disp,
                  double percentile, void* stream);
+
+/* Ground-truth depth maps from Velodyne scans (kitti_utils.py:46-98, generate_depth_map), a ragged batch of n_frames
+ * frames per call, written straight into a packed float32 buffer such as evaluation.GroundTruthSet keeps.
+ *   points  float32 [total points, 4]: x, y, z and a fourth column that is ignored (KITTI's reflectance, which the
+ *           reference overwrites with 1) - the .bin files as they are on disk, frames back to back, 16-byte aligned
+ *   desc[f] = {out offset lo, hi (elements of `out`), h, w, n_points, first point, first pixel of the frame's scratch, 0}
+ *   proj[f] = P_rect_0c . R_cam2rect . velo2cam, float64 [3,4] row-major
+ * For every point with x >= 0, in float64 (operation order: bbd_velo_math.h): q = P (x, y, z, 1),
+ * u = rint(q0/q2) - 1, v = rint(q1/q2) - 1, depth = x with BBD_VELO_VEL_DEPTH, else q2; the point is valid when
+ * 0 <= u < w and 0 <= v < h.  out[v, u] is the depth of the LAST valid point on the pixel; then, for every key
+ * v * (w-1) + u - 1 hit by more than one valid point, the pixel of the key's FIRST point takes the MINIMUM depth of
+ * the key.  The key is the reference's sub2ind and is not unique - (r, w-1) and (r+1, 0) share one - which is
+ * reproduced on purpose.  Negative depths become 0; values are the float32 casts of the float64 ones.  Every pixel of
+ * every frame is written.
+ * scratch holds scratch_ints = bbd_velo_depth_scratch_ints(sum of h*w, n_frames) int32 and is zeroed on `stream` by
+ * the call; a frame whose tables would not fit in scratch_ints is skipped.  One memset and two launches (a point
+ * sweep over ceil(max_points / 256) x n_frames workgroups, max_points >= every n_points; a pixel sweep), integer
+ * atomics only: the result depends on the order of the points, not on launch geometry or scheduling.  No host
+ * synchronisation.  n_frames <= 65535. */
+#define BBD_VELO_DESC 8
+#define BBD_VELO_VEL_DEPTH 1
+int bbd_velo_depth_scratch_ints(int total_pixels, int n_frames);
+int bbd_velo_depth(const float* points, const int32_t* desc, const double* proj, int32_t* scratch, int scratch_ints,
+                   float* out, int n_frames, int max_points, int flags, void* stream);
 
 /* ---- Loader image pipeline: replaces the per-item Pillow/torchvision work of
  * datasets/mono_dataset.py:186-205 (Resize(LANCZOS) chain, ColorJitter, ToTensor) and the stacking of

@@ -1,0 +1,192 @@
+"""CPU tier of the Velodyne depth maps: the host port of bbd_velo.hip (same bbd_velo_math.h) driven through the
+`backend=` seam of `ops.velo_depth`, `kitti_utils.generate_depth_maps` and the export command line, against maps
+recorded from the reference (tools/make_golden_velo.py).  Acceptance rules: tests/velo_checks.py."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import velo_checks as vc  # noqa: E402
+from velo_port import VeloPortBackend  # noqa: E402
+from baseboostdepth_amd import kitti_utils, ops  # noqa: E402
+from baseboostdepth_amd.evaluation import GroundTruthSet  # noqa: E402
+
+EVERY = [(c, cam) for c in vc.CASES for cam in vc.CAMS]
+
+
+@pytest.fixture(scope="module")
+def port():
+    return VeloPortBackend()
+
+
+@pytest.fixture(scope="module")
+def v():
+    return vc.load()
+
+
+def test_fixture_holds_what_the_tests_rely_on(v):
+    assert vc.size(v, "scan_a") == (375, 1242) and vc.size(v, "scan_b") == (370, 1226)      # a ragged batch
+    for c in ("scan_a", "scan_b"):
+        assert (vc.golden_map(v, c, 2, True) != 0).sum() > 15000
+    assert len(v["empty/points"]) == 0 and not vc.golden_map(v, "empty", 2, True).any()
+    h, w = vc.size(v, "crafted")
+    m = vc.golden_map(v, "crafted", 2, True)
+    # the (r, w-1) / (r+1, 0) key collision as the reference resolves it: both pixels of a key whose first point sits on
+    # one side and whose minimum on the other carry the minimum; with one point each the first takes the minimum of both
+    assert m[200, w - 1] == m[201, 0] and 9 < m[201, 0] < 10
+    assert 7 < m[101, 0] < 8 and 22 < m[100, w - 1] < 23          # the first point's pixel takes the other's 7, not its own 11
+    assert m[250, w - 1] < m[251, 0] and m[261, 0] < m[260, w - 1]
+    assert m[271, 0] == m[270, w - 1] and m[281, w - 1] == m[282, 0]
+    assert (vc.bits(m) == 0x80000000).sum() >= 1                 # x = -0.0 passes the filter and is recorded as -0.0
+    pts = v["crafted/points"]
+    assert np.isnan(pts).any() and np.isinf(pts).any() and (pts[:, 0] < 0).any()
+
+
+@pytest.mark.parametrize("vel_depth", [True, False])
+@pytest.mark.parametrize("case,cam", EVERY)
+def test_single_frame_matches_the_reference(port, v, case, cam, vel_depth):
+    (got,), _ = vc.run_batch(v, [(case, cam)], vel_depth, port, "cpu")
+    vc.check_map(got, vc.golden_map(v, case, cam, vel_depth), vel_depth, "%s cam %d" % (case, cam))
+
+
+@pytest.mark.parametrize("vel_depth", [True, False])
+def test_ragged_batch_matches_the_reference_and_single_calls(port, v, vel_depth):
+    """Every case and both cameras in ONE call: sizes, point counts and projections differ per frame."""
+    maps, _ = vc.run_batch(v, EVERY, vel_depth, port, "cpu")
+    for (case, cam), got in zip(EVERY, maps):
+        vc.check_map(got, vc.golden_map(v, case, cam, vel_depth), vel_depth, "%s cam %d (batched)" % (case, cam))
+        (one,), _ = vc.run_batch(v, [(case, cam)], vel_depth, port, "cpu")
+        assert np.array_equal(vc.bits(one), vc.bits(got))
+
+
+def test_output_offsets_are_honoured_and_every_pixel_is_written(port, v):
+    """Frames written into a caller's buffer in another order; the buffer starts as NaN and is not cleared."""
+    members = [("scan_b", 2), ("crafted", 3)]
+    sizes = [h * w for h, w in (vc.size(v, c) for c, _ in members)]
+    out = torch.full((sum(sizes) + 7,), float("nan"))
+    offsets = [sizes[1] + 7, 0]
+    maps, buf = vc.run_batch(v, members, True, port, "cpu", out=out, offsets=offsets)
+    assert buf is out and torch.isnan(out[sizes[1]:sizes[1] + 7]).all() and not torch.isnan(out).sum() > 7
+    for (case, cam), got in zip(members, maps):
+        vc.check_map(got, vc.golden_map(v, case, cam, True), True)
+
+
+def test_velo_projection_equals_the_recorded_matrices(v, tmp_path):
+    for name in ("2011_09_26", "2011_09_30", "axis_aligned"):
+        d = vc.write_calibration(v, str(tmp_path), name)
+        case = [c for c in vc.CASES if str(v[c + "/calib"]) == name][0]
+        for cam in vc.CAMS:
+            P, hw = kitti_utils.velo_projection(d, cam)
+            assert P.dtype == np.float64 and P.shape == (3, 4) and hw == vc.size(v, case)
+            np.testing.assert_allclose(P, v["%s/P%d" % (case, cam)], rtol=1e-12, atol=0)
+    calib = kitti_utils.read_calib_file(os.path.join(d, "calib_cam_to_cam.txt"))
+    assert calib["calib_time"] == "none" and calib["S_rect_02"].tolist() == [1242.0, 375.0]
+
+
+def test_load_velodyne_points_makes_the_last_column_homogeneous(v, tmp_path):
+    path = str(tmp_path / "scan.bin")
+    vc.scan(v, "crafted").tofile(path)
+    pts = kitti_utils.load_velodyne_points(path)
+    assert pts.dtype == np.float32 and pts.shape == (len(v["crafted/points"]), 4) and (pts[:, 3] == 1).all()
+    assert np.array_equal(vc.bits(pts[:, :3]), vc.bits(v["crafted/points"]))
+
+
+def _tree(v, root, ragged):
+    frames = [("2011_09_26", 0, vc.scan(v, "scan_a")), ("2011_09_26", 5, vc.scan(v, "crafted"))]
+    cases = ["scan_a", "crafted"]
+    if ragged:
+        frames += [("2011_09_30", 3, vc.scan(v, "scan_b")), ("2011_09_30", 4, vc.scan(v, "empty"))]
+        cases += ["scan_b", "empty"]
+    return vc.write_tree(v, root, frames), cases
+
+
+def test_generate_depth_maps_returns_the_ground_truth_set_of_the_golden_maps(port, v, tmp_path):
+    root = str(tmp_path)
+    lines, cases = _tree(v, root, ragged=True)
+    vc.write_split(root, "eigen", lines)
+    frames = kitti_utils.split_frames(os.path.join(root, "eigen"), "eigen", root)
+    for batch_frames in (32, 3):                     # one launch, and batches that cut the list unevenly
+        gts = kitti_utils.generate_depth_maps(frames, "cpu", vel_depth=True, backend=port, batch_frames=batch_frames)
+        want = GroundTruthSet([vc.golden_map(v, c, 2, True) for c in cases], "cpu")
+        assert isinstance(gts, GroundTruthSet) and gts.shapes == want.shapes and len(gts) == 4
+        assert torch.equal(gts.desc, want.desc)
+        assert np.array_equal(vc.bits(gts.buffer.numpy()), vc.bits(want.buffer.numpy()))
+    one = kitti_utils.generate_depth_map(frames[2][0], frames[2][1], cam=3, vel_depth=False, device="cpu", backend=port)
+    vc.check_map(one, vc.golden_map(v, "scan_b", 3, False), False, "generate_depth_map")
+
+
+@pytest.mark.parametrize("crop", [True, False])
+def test_from_packed_builds_the_descriptors_of_the_constructor(crop):
+    rng = np.random.default_rng(1)
+    maps = [rng.random(s).astype(np.float32) for s in ((375, 1242), (370, 1226), (5, 9), (375, 1242))]
+    want = GroundTruthSet(maps, "cpu", crop=crop)
+    got = GroundTruthSet.from_packed(want.buffer.clone(), [m.shape for m in maps], crop=crop)
+    assert torch.equal(got.desc, want.desc) and got.desc.dtype == want.desc.dtype
+    assert got.shapes == want.shapes and len(got) == 4 and torch.equal(got.buffer, want.buffer)
+    with pytest.raises(AssertionError):
+        GroundTruthSet.from_packed(want.buffer[:-1].clone(), [m.shape for m in maps])
+
+
+@pytest.mark.parametrize("split,ragged", [("eigen", False), ("eigen", True), ("eigen_zhou", True)])
+def test_export_writes_the_npz_the_reference_writes(port, v, tmp_path, split, ragged):
+    root, splits = str(tmp_path / "kitti"), str(tmp_path / "splits")
+    lines, cases = _tree(v, root, ragged)
+    vc.write_split(splits, split, lines)
+    path = kitti_utils.export_main(["--data_path", root, "--split", split, "--splits_dir", splits, "--device", "cpu"],
+                                   backend=port)
+    assert path == os.path.join(splits, split, "gt_depths.npz")
+    data = np.load(path, fix_imports=True, encoding="latin1", allow_pickle=True)["data"]      # evaluation.evaluate's call
+    if ragged:
+        assert data.dtype == object and data.shape == (4,)
+    else:
+        assert data.dtype == np.float32 and data.shape == (2, 375, 1242)
+    for got, c in zip(data, cases):
+        vc.check_map(got, vc.golden_map(v, c, 2, True), True, c)
+    other = str(tmp_path / "elsewhere.npz")
+    assert kitti_utils.export_main(["--data_path", root, "--split", split, "--splits_dir", splits, "--device", "cpu",
+                                    "--output", other], backend=port) == other
+    assert os.path.isfile(other)
+
+
+def test_export_reads_the_benchmark_pngs_on_the_host(tmp_path):
+    from PIL import Image
+    root, splits = str(tmp_path / "kitti"), str(tmp_path / "splits")
+    rng = np.random.default_rng(3)
+    lines, want = [], []
+    for t in (2, 9):
+        d = os.path.join(root, vc.DRIVES["2011_09_26"], "proj_depth", "groundtruth", "image_02")
+        os.makedirs(d, exist_ok=True)
+        raw = (rng.integers(0, 20000, (30, 50)) * (rng.random((30, 50)) < 0.3)).astype(np.uint16)
+        Image.fromarray(raw).save(os.path.join(d, "%010d.png" % t))
+        lines.append("%s %d l" % (vc.DRIVES["2011_09_26"], t))
+        want.append(raw.astype(np.float32) / 256)
+    vc.write_split(splits, "eigen_benchmark", lines)
+    path = kitti_utils.export_main(["--data_path", root, "--split", "eigen_benchmark", "--splits_dir", splits])
+    data = np.load(path)["data"]
+    assert data.dtype == np.float32 and np.array_equal(data, np.stack(want))
+
+
+def test_export_refuses_syns(capsys):
+    with pytest.raises(SystemExit) as e:
+        kitti_utils.export_main(["--data_path", "x", "--split", "SYNS"])
+    assert e.value.code == 2 and "outside this build's scope" in capsys.readouterr().err
+
+
+def test_root_script_is_the_command_line():
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "export_gt_depth.py"), "--data_path", "x", "--split", "SYNS"],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "SYNS" in r.stderr and "scope" in r.stderr
+
+
+def test_hip_backend_refuses_cpu_tensors(v):
+    from baseboostdepth_amd import _lib
+    from baseboostdepth_amd.csrc.build import build
+    build()
+    with pytest.raises(_lib.BbdError):
+        vc.run_batch(v, [("crafted", 2)], True, ops.HipBackend(), "cpu")
