@@ -20,7 +20,7 @@ PROJ_STRIDE = 24
 KIND_WARP, KIND_IDENT, FLAG_NO_POSE_GRAD = 0, 1, 0x100
 COMPOSE_STRIDE, COMPOSE_ERROR, COMPOSE_REPLACE = 12, 1, 2
 PAIR_SHIFT = 16        # bits 16-23 of bbd_cand_t.kind: 1 + index of the pass partner (hint), 0 = none
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 _p = ctypes.c_void_p
 _i = ctypes.c_int
@@ -66,6 +66,12 @@ SIGNATURES = {
     "bbd_disp_viz": [_p] * 7 + [_i, _i, _i, _d, _d, _d, _p],
     "bbd_velo_depth_scratch_ints": [_i, _i],
     "bbd_velo_depth": [_p, _p, _p, _p, _i, _p, _i, _i, _i, _p],
+    "bbd_syns_scratch_ints": [_i, _i],
+    "bbd_syns_pred_edges": [_p, _p, _p, _i, _p, _p] + [_i] * 6 + [_d, _d, _i, _p],
+    "bbd_syns_edt": [_p, _p, _p, _i, _i, _i, _i, _p],
+    "bbd_syns_edge_metrics": [_p] * 7 + [_i, _p] + [_i] * 6 + [_d] * 6 + [_i, _p],
+    "bbd_chamfer_nn": [_p, _p, _i, _i, _p, _p, _p],
+    "bbd_syns_pointcloud": [_p] * 6 + [_i, _p] + [_i] * 6 + [_d] * 5 + [_i, _p],
     "bbd_resample_h_u8": [_p, _p, _p, _i, _i, _p, _p, _i, _p],
     "bbd_resample_v_u8": [_p, _p, _p, _i, _i, _i, _p, _p, _i, _p],
     "bbd_color_jitter_u8": [_p, _p, _p, _i, _i, _i, _p, _p],
@@ -115,6 +121,7 @@ RESAMPLE_JOB, RESAMPLE_FLIP, JITTER_JOB, CONVERT_JOB = 12, 1, 12, 4
 EVAL_DESC, EVAL_OUT = 8, 12
 VIZ_DESC = 4
 VELO_DESC, VELO_VEL_DEPTH = 8, 1
+SYNS_OUT, SYNS_CLOUD_OUT, SYNS_RAYS_PIXEL = 8, 8, 8
 EVAL_PRED_IS_DISP, EVAL_MEDIAN_MIDPOINT, EVAL_NO_MEDIAN_SCALING = 1, 2, 4
 
 
@@ -187,6 +194,9 @@ class HipLibrary:
 
     def velo_depth_scratch_ints(self, total_pixels, n_frames):
         return self._dll.bbd_velo_depth_scratch_ints(total_pixels, n_frames)
+
+    def syns_scratch_ints(self, n, px_stride):
+        return self._dll.bbd_syns_scratch_ints(n, px_stride)
 
     def dispconv_scratch_doubles(self, C):
         return self._dll.bbd_dispconv_scratch_doubles(C)

@@ -16,6 +16,7 @@
 
 #include "../../include/bbd_hip.h"
 #include "bbd_math.h"
+#include "bbd_eval_math.h"
 
 namespace {
 
@@ -41,41 +42,9 @@ __device__ __forceinline__ float key_value(uint32_t k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
-// Prediction at ground-truth pixel (y, x) of a GH x GW map.
+// Prediction at ground-truth pixel (y, x) of a GH x GW map (bbd_eval_math.h, shared with bbd_syns.hip).
 __device__ __forceinline__ float resample(const EvalArgs& a, const float* img, int y, int x, int GH, int GW) {
-  if (a.flags & BBD_EVAL_PRED_IS_DISP) {
-    // cv2.resize(pred_disp, (gt_width, gt_height)) - INTER_LINEAR on float32 (evaluate_depth.py:248):
-    // half-pixel centres, coordinate in double -> float, edge taps collapse to weight 0, horizontal
-    // pass then vertical pass, products and sums rounded separately; then pred_depth = 1 / pred_disp.
-    const double sx_ = (double)a.w / (double)GW, sy_ = (double)a.h / (double)GH;
-    float fx = (float)(((double)x + 0.5) * sx_ - 0.5);
-    float fy = (float)(((double)y + 0.5) * sy_ - 0.5);
-    int ix = (int)floorf(fx), iy = (int)floorf(fy);
-    fx -= (float)ix;
-    fy -= (float)iy;
-    if (ix < 0) { ix = 0; fx = 0.0f; }
-    if (ix >= a.w - 1) { ix = a.w - 1; fx = 0.0f; }
-    if (iy < 0) { iy = 0; fy = 0.0f; }
-    if (iy >= a.h - 1) { iy = a.h - 1; fy = 0.0f; }
-    const int ix1 = ix < a.w - 1 ? ix + 1 : ix, iy1 = iy < a.h - 1 ? iy + 1 : iy;
-    const float* r0 = img + (size_t)iy * a.w;
-    const float* r1 = img + (size_t)iy1 * a.w;
-    const float top = r0[ix] * (1.0f - fx) + r0[ix1] * fx;
-    const float bot = r1[ix] * (1.0f - fx) + r1[ix1] * fx;
-    const float d = top * (1.0f - fy) + bot * fy;
-    return (1.0f / d) * a.scale_factor;            // evaluate_depth.py:252, :275
-  }
-  // F.interpolate(depth_pred, [gt_h, gt_w], bilinear, align_corners=False) then clamp (trainer.py:599)
-  int y0, y1, x0, x1;
-  float ly0, ly1, lx0, lx1;
-  bbd_up_src(y, a.h, GH, &y0, &y1, &ly0, &ly1);
-  bbd_up_src(x, a.w, GW, &x0, &x1, &lx0, &lx1);
-  const float* r0 = img + (size_t)y0 * a.w;
-  const float* r1 = img + (size_t)y1 * a.w;
-  float v = bbd_up_blend(r0[x0], r0[x1], r1[x0], r1[x1], ly0, ly1, lx0, lx1, GH + GW <= 128);
-  v = v < a.clamp_lo ? a.clamp_lo : v;             // torch.clamp: NaN propagates
-  v = v > a.clamp_hi ? a.clamp_hi : v;
-  return v;
+  return bbd_eval_resample(img, a.h, a.w, a.scale_factor, a.clamp_lo, a.clamp_hi, a.flags, y, x, GH, GW);
 }
 
 __device__ __forceinline__ double wave_sum(double v) {

@@ -196,6 +196,41 @@ class KITTIRAWDataset(KITTIDataset):
                             "{:010d}{}".format(frame_index, ".jpg"))
 
 
+class SYNSRAWDataset(MonoDataset):
+    """SYNS-Patches, evaluation items only (syns_dataset.py): split lines are `folder frame`, the image is
+    `<syns_path>/images/<folder>/<frame>.png`.  Items have the form `DeviceCollate` / `DeviceLoader` take, so the
+    frames go through the same device loader as KITTI's.  `K` / `inv_K` are the camera the reference back-projects the
+    point clouds with (`load_intrinsic_syns`)."""
+    FOV = (25.46, 84.10)              # (vertical, horizontal) degrees
+    SHAPE = (376, 1242)
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        if self.is_train:
+            raise ValueError("SYNS-Patches is an evaluation set: there are no training items")
+        self.K, self.inv_K = self.load_intrinsic_syns()
+
+    @classmethod
+    def load_intrinsic_syns(cls):
+        """syns_dataset.py:20-38."""
+        Fy, Fx = cls.FOV
+        h, w = cls.SHAPE
+        cx, cy = w // 2, h // 2
+        fx = cx / np.tan(np.deg2rad(Fx) / 2)
+        fy = cy / np.tan(np.deg2rad(Fy) / 2)
+        K = np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], dtype=np.float32)
+        return K, np.linalg.pinv(K)
+
+    def index_to_folder_and_frame_idx_kt(self, index):
+        """syns_dataset.py:44-47 (the frame is a name, not a number; there is one camera)."""
+        folder, frame_index = self.filenames[index].split()
+        return folder, frame_index, None
+
+    def get_image_path_kt(self, data_path, frame_index, side, folder):
+        """syns_dataset.py:55-58; `data_path` is ignored: the set lives under `syns_path`."""
+        return os.path.join(self.syns_path, "images", folder, "{}.png".format(frame_index))
+
+
 class FrameCache:
     """Decoded frames kept resident in HBM (uint8 HWC, as decoded).
 

@@ -5,13 +5,19 @@ one buffer plus an int descriptor table, so scoring an image is one kernel launc
 round trip - the reference re-uploads the map, builds the crop mask in numpy, gathers with it and
 sorts twice per image (trainer.py:594-617, evaluate_depth.py:244-297).
 
-`depth_metrics` is the single entry: one `bbd_depth_metrics` launch for a batch of predictions.
+`depth_metrics` is the single entry for the KITTI metrics: one `bbd_depth_metrics` launch for a batch of predictions.
+
+The SYNS-Patches metrics (evaluate_depth.py:26-102 with `--eval_split SYNS [--chamfer]`) are layered on it, each
+layer callable on its own: `pred_edges` (log, blur, Sobel, threshold), `distance_transform` (exact squared Euclidean
+distance maps), `edge_metrics` (edge accuracy / completeness and `err`), `pointcloud_metrics` (F-score and IoU of the
+back-projected clouds, all-pairs nearest neighbour) and `syns_metrics`, the reference's 9-column row.
 """
 import numpy as np
 import torch
 
 from . import ops
-from ._lib import (EVAL_DESC, EVAL_OUT, EVAL_PRED_IS_DISP, EVAL_MEDIAN_MIDPOINT, EVAL_NO_MEDIAN_SCALING, ptr)
+from ._lib import (EVAL_DESC, EVAL_OUT, EVAL_PRED_IS_DISP, EVAL_MEDIAN_MIDPOINT, EVAL_NO_MEDIAN_SCALING, SYNS_OUT,
+                   SYNS_CLOUD_OUT, SYNS_RAYS_PIXEL, BbdError, ptr)
 
 METRIC_NAMES = ["de/abs_rel", "de/sq_rel", "de/rms", "de/log_rms", "da/a1", "da/a2", "da/a3"]   # trainer.py:156
 GARG_CROP = (0.40810811, 0.99189189, 0.03594771, 0.96405229)     # trainer.py:603-604
@@ -26,9 +32,18 @@ def garg_window(gh, gw):
 class GroundTruthSet:
     """Ragged ground-truth depth maps of a split, packed once into device memory."""
 
-    def __init__(self, gt_depths, device, crop=True):
+    def __init__(self, gt_depths, device, crop=True, edges=None):
+        """`edges` (SYNS: gt_edges.npz, maps of shape [GH,GW] or [GH,GW,1], non-zero = edge) are packed as bytes at
+        the same offsets as the depth maps; without them the set is what it always was."""
         maps = [np.ascontiguousarray(np.asarray(g, dtype=np.float32)) for g in gt_depths]
         assert all(m.ndim == 2 for m in maps)
+        self.edges = None
+        if edges is not None:
+            em = [np.asarray(e) for e in edges]
+            em = [(e[..., 0] if e.ndim == 3 else e) != 0 for e in em]
+            assert len(em) == len(maps) and all(e.shape == m.shape for e, m in zip(em, maps))
+            flat_e = np.concatenate([e.ravel() for e in em]).astype(np.uint8) if em else np.zeros(0, np.uint8)
+            self.edges = torch.from_numpy(flat_e).to(device)
         desc = np.zeros((len(maps), EVAL_DESC), dtype=np.int32)
         off = 0
         for i, m in enumerate(maps):
@@ -56,6 +71,7 @@ class GroundTruthSet:
             desc[i] = (off & 0xFFFFFFFF if off < 2 ** 31 else (off & 0xFFFFFFFF) - 2 ** 32, off >> 32, gh, gw) + win
             off += gh * gw
         self = cls.__new__(cls)
+        self.edges = None
         self.shapes = shapes
         self.buffer = buffer
         self.desc = torch.from_numpy(desc).to(buffer.device)
@@ -88,11 +104,170 @@ def depth_metrics(pred, gts, indices, min_depth=1e-3, max_depth=80.0, clamp=(1e-
     return out
 
 
+# ---------------------------------------------------------------------------- SYNS-Patches metrics
+SYNS_MIN_DEPTH, SYNS_MAX_DEPTH = 1e-3, 125.0        # evaluate_depth.py:107-109
+SYNS_EDGE_TH, SYNS_CLOUD_TH = 10.0, 0.1             # evaluate_depth.py:90, :85
+SYNS_COLUMNS = ["abs_rel", "err", "sq_rel", "rmse", "rmse_log", "edge_Acc", "edge_comp", "f1", "iou1"]
+
+
+class _SynsCall:
+    """What every SYNS launch needs: the batch's descriptor rows and the strides that size the launches.  The strides
+    come from the largest map of the WHOLE set, which the host knows without asking the device."""
+
+    def __init__(self, pred, gts, indices, backend):
+        self.backend = backend or ops.default_backend()
+        pred = pred.detach()
+        if pred.dim() == 4:
+            assert pred.shape[1] == 1
+            pred = pred[:, 0]
+        self.pred = pred.contiguous().float()
+        self.backend._check(self.pred, gts.buffer)
+        self.n, self.h, self.w = self.pred.shape
+        idx = torch.as_tensor(indices, dtype=torch.long, device=gts.desc.device).view(-1)
+        assert idx.numel() == self.n
+        self.desc = gts.desc.index_select(0, idx).contiguous()
+        self.max_h, self.max_w, self.px_stride = syns_strides(gts)
+        self.n_ints = self.backend.lib.syns_scratch_ints(self.n, self.px_stride)
+        if self.n_ints < 0:
+            raise BbdError("SYNS metrics: %d images of up to %d pixels are more than one scratch buffer holds; "
+                           "split the batch" % (self.n, self.px_stride))
+
+    def scratch(self):
+        return torch.empty(self.n_ints, dtype=torch.int32, device=self.pred.device)
+
+    def sizes(self):
+        return self.n, self.h, self.w, self.px_stride, self.max_h, self.max_w
+
+
+def syns_strides(gts):
+    """(max GH, max GW, elements per image slot) of a set: the slot holds max GH x max GW, rounded up to 4 elements."""
+    max_h, max_w = max(s[0] for s in gts.shapes), max(s[1] for s in gts.shapes)
+    return max_h, max_w, (max_h * max_w + 3) // 4 * 4
+
+
+def image_view(buf, gts, index, row):
+    """Row `row` of a strided per-image buffer ([n, px_stride]) as the [GH, GW] map of gts[index]."""
+    gh, gw = gts.shapes[int(index)]
+    return buf[row, :gh * gw].view(gh, gw)
+
+
+def pred_edges(pred, gts, indices, pred_is_disp=False, clamp=(1e-3, 80.0), backend=None):
+    """evaluate_depth.py:260-265 / trainer.py:580-588 on the device: the prediction at ground-truth size (as
+    `depth_metrics` resamples it), to_log, GaussianBlur 3x3 sigma 1, 5x5 Sobel in float64, magnitude > its mean.
+    Returns (edge uint8 [n, px_stride], stats float64 [n, 2] = mean magnitude, number of edge pixels);
+    `image_view(edge, gts, indices[i], i)` is image i's map."""
+    c = _SynsCall(pred, gts, indices, backend)
+    dev = c.pred.device
+    edge = torch.zeros(c.n, c.px_stride, dtype=torch.uint8, device=dev)
+    stats = torch.empty(c.n, 2, dtype=torch.float64, device=dev)
+    scratch = c.scratch()
+    c.backend.run("bbd_syns_pred_edges", c.pred, ptr(c.pred), ptr(c.desc), ptr(scratch), c.n_ints, ptr(edge),
+                  ptr(stats), *c.sizes(), float(clamp[0]), float(clamp[1]), EVAL_PRED_IS_DISP if pred_is_disp else 0)
+    return edge, stats
+
+
+def distance_transform(maps, gts, indices, backend=None):
+    """Exact SQUARED Euclidean distance (int32 [n, px_stride]) of every pixel to the nearest non-zero byte of
+    maps[i] (uint8 [n, px_stride], image i shaped as gts[indices[i]]): scipy's distance_transform_edt(1 - map) ** 2.
+    A map without a non-zero byte gives 2 ** 30 everywhere."""
+    backend = backend or ops.default_backend()
+    assert maps.dtype == torch.uint8 and maps.dim() == 2 and maps.is_contiguous()
+    backend._check(maps)
+    max_h, max_w, px_stride = syns_strides(gts)
+    assert maps.shape[1] == px_stride
+    idx = torch.as_tensor(indices, dtype=torch.long, device=gts.desc.device).view(-1)
+    assert idx.numel() == maps.shape[0]
+    desc = gts.desc.index_select(0, idx).contiguous()
+    out = torch.zeros(maps.shape, dtype=torch.int32, device=maps.device)
+    backend.run("bbd_syns_edt", maps, ptr(maps), ptr(desc), ptr(out), maps.shape[0], px_stride, max_h, max_w)
+    return out
+
+
+def _eval_flags(pred_is_disp, median_scaling):
+    return (EVAL_PRED_IS_DISP if pred_is_disp else 0) | (0 if median_scaling else EVAL_NO_MEDIAN_SCALING)
+
+
+def edge_metrics(pred, gts, indices, edge, rows, min_depth=SYNS_MIN_DEPTH, max_depth=SYNS_MAX_DEPTH,
+                 clamp=(1e-3, 80.0), pred_is_disp=False, median_scaling=True, scale_factor=1.0, th=SYNS_EDGE_TH,
+                 backend=None):
+    """evaluate_depth.py:72-73, :89-95: float64 [n, 8] = edge_Acc, edge_comp, err, count(near), count(target),
+    count(valid), count(predicted edge), 0.  `edge` is `pred_edges`' map, `rows` the `depth_metrics` rows of the same
+    batch (their ratio is read on the device).  Both edge metrics are `th` when no predicted edge lies within `th`
+    of a target edge, and NaN when the image has no valid ground-truth edge pixel at all: scipy's transform of a map
+    without background is an artefact of its implementation, not a distance."""
+    assert gts.edges is not None, "this GroundTruthSet was built without edge maps"
+    c = _SynsCall(pred, gts, indices, backend)
+    assert edge.dtype == torch.uint8 and edge.shape == (c.n, c.px_stride) and edge.is_contiguous()
+    assert rows.dtype == torch.float32 and rows.shape == (c.n, EVAL_OUT) and rows.is_contiguous()
+    c.backend._check(edge, rows, gts.edges)
+    out = torch.empty(c.n, SYNS_OUT, dtype=torch.float64, device=c.pred.device)
+    scratch = c.scratch()
+    c.backend.run("bbd_syns_edge_metrics", c.pred, ptr(c.pred), ptr(gts.buffer), ptr(gts.edges), ptr(edge), ptr(c.desc),
+                  ptr(rows), ptr(scratch), c.n_ints, ptr(out), *c.sizes(), float(min_depth), float(max_depth),
+                  float(clamp[0]), float(clamp[1]), float(scale_factor), float(th),
+                  _eval_flags(pred_is_disp, median_scaling))
+    return out
+
+
+def pointcloud_metrics(pred, gts, indices, rows, inv_K, min_depth=SYNS_MIN_DEPTH, max_depth=SYNS_MAX_DEPTH,
+                       clamp=(1e-3, 80.0), pred_is_disp=False, median_scaling=True, rays="reference",
+                       th=SYNS_CLOUD_TH, backend=None):
+    """evaluate_depth.py:74-85 with `--chamfer`: float32 [n, 8] = f1, iou, precision, recall, count(pred within th),
+    count(gt within th), points per cloud, 0.  Both clouds hold the valid ground-truth pixels only.
+
+    rays="reference" pairs flat pixel k (row-major) with the ray of pixel (k // GH, k % GH): the reference builds its
+    grid with torch.meshgrid(arange(w), arange(h)) in ij order and flattens it against the row-major depth map, so
+    every published number carries that pairing.  rays="pixel" uses the pixel's own ray (k % GW, k // GW)."""
+    assert rays in ("reference", "pixel")
+    c = _SynsCall(pred, gts, indices, backend)
+    assert rows.dtype == torch.float32 and rows.shape == (c.n, EVAL_OUT) and rows.is_contiguous()
+    iK = torch.as_tensor(np.asarray(inv_K, dtype=np.float32)[:3, :3].copy()).contiguous().to(c.pred.device)
+    c.backend._check(rows, iK)
+    out = torch.empty(c.n, SYNS_CLOUD_OUT, dtype=torch.float32, device=c.pred.device)
+    scratch = c.scratch()
+    c.backend.run("bbd_syns_pointcloud", c.pred, ptr(c.pred), ptr(gts.buffer), ptr(c.desc), ptr(rows), ptr(iK),
+                  ptr(scratch), c.n_ints, ptr(out), *c.sizes(), float(min_depth), float(max_depth), float(clamp[0]),
+                  float(clamp[1]), float(th),
+                  _eval_flags(pred_is_disp, median_scaling) | (SYNS_RAYS_PIXEL if rays == "pixel" else 0))
+    return out
+
+
+def syns_metrics(pred, gts, indices, inv_K=None, chamfer=False, mode="evaluate", median_scaling=True,
+                 scale_factor=1.0, rays="reference", backend=None, return_rows=False):
+    """One SYNS-Patches row per image, float64 [n, 9] on the device, in the reference's column order
+    (`SYNS_COLUMNS`): abs_rel, err, sq_rel, rmse, rmse_log, edge_Acc, edge_comp, f1, iou1; the last two are NaN
+    without `chamfer`.  Nothing synchronises with the host.
+
+    mode="evaluate" is evaluate_depth.py: `pred` is a disparity, resized as cv2 does, depth range (1e-3, 125),
+    np.median scaling, no crop.  mode="trainer" is Trainer.compute_depth_losses(SYNS=True) (trainer.py:576-617):
+    `pred` is a depth, F.interpolate then clamp to [1e-3, 80], depth range (1e-3, 80), torch.median.
+    `gts` must have been built with `crop=False` and `edges=`."""
+    assert mode in ("evaluate", "trainer")
+    ev = mode == "evaluate"
+    lo, hi = (SYNS_MIN_DEPTH, SYNS_MAX_DEPTH) if ev else (1e-3, 80.0)
+    rows = depth_metrics(pred, gts, indices, min_depth=lo, max_depth=hi, pred_is_disp=ev,
+                         median="numpy" if ev else "torch", median_scaling=median_scaling, scale_factor=scale_factor,
+                         backend=backend)
+    edge, _ = pred_edges(pred, gts, indices, pred_is_disp=ev, backend=backend)
+    em = edge_metrics(pred, gts, indices, edge, rows, min_depth=lo, max_depth=hi, pred_is_disp=ev,
+                      median_scaling=median_scaling, scale_factor=scale_factor, backend=backend)
+    out = torch.full((rows.shape[0], 9), float("nan"), dtype=torch.float64, device=rows.device)
+    r64 = rows.double()
+    out[:, 0], out[:, 1], out[:, 2], out[:, 3], out[:, 4] = r64[:, 0], em[:, 2], r64[:, 1], r64[:, 2], r64[:, 3]
+    out[:, 5], out[:, 6] = em[:, 0], em[:, 1]
+    if chamfer:
+        assert inv_K is not None, "the point-cloud metrics need the camera's inverse intrinsics"
+        pc = pointcloud_metrics(pred, gts, indices, rows, inv_K, min_depth=lo, max_depth=hi, pred_is_disp=ev,
+                                median_scaling=median_scaling, rays=rays, backend=backend)
+        out[:, 7], out[:, 8] = pc[:, 0].double(), pc[:, 1].double()
+    return (out, rows) if return_rows else out
+
+
 # ---------------------------------------------------------------------------- evaluate_depth.py
 STEREO_SCALE_FACTOR = 5.4          # evaluate_depth.py:45
 
 
-def evaluate(opt, dataloader=None, gt_depths=None, models=None, batch_size=16):
+def evaluate(opt, dataloader=None, gt_depths=None, models=None, batch_size=16, gt_edges=None, inv_K=None):
     """KITTI branch of the reference's `evaluate(opt)` (evaluate_depth.py:104-317) for the ResNet and MonoViT (`--ViT`) models:
     predicts disparities for a split, scores them against `gt_depths.npz` with median (mono) or 5.4x
     (stereo) scaling, returns (mean_errors[7], ratios).  Differences by design: images are prepared by the
@@ -103,7 +278,12 @@ def evaluate(opt, dataloader=None, gt_depths=None, models=None, batch_size=16):
     built from `opt.splits_dir/<eval_split>/{test_files.txt, gt_depths.npz}`, `opt.kt_path` and
     `opt.load_weights_folder`.  Where `gt_depths.npz` does not exist (the reference ships none) and the split is `eigen`
     or `eigen_zhou`, the ground truth is projected from the Velodyne scans under `opt.kt_path` on the device
-    (`kitti_utils.generate_depth_maps`: what `export_gt_depth.py` writes, without the file)."""
+    (`kitti_utils.generate_depth_maps`: what `export_gt_depth.py` writes, without the file).
+
+    `opt.eval_split == "SYNS"` is the reference's SYNS-Patches branch: frames from `opt.syns_path`, `gt_depths.npz` and
+    `gt_edges.npz` from the split directory (or `gt_depths` / `gt_edges`), depth range (1e-3, 125), no crop, and the
+    7-column table abs_rel, err, sq_rel, rmse, rmse_log, edge_Acc, edge_comp - 9 columns with f1 and iou1 under
+    `opt.chamfer` (`syns_metrics`).  Returns (mean_errors[7 or 9], ratios)."""
     from . import tuning
     tuning.use_shipped_db()      # (no Trainer is built here: the tuned MIOpen database is wired explicitly)
     import os
@@ -135,12 +315,19 @@ def evaluate(opt, dataloader=None, gt_depths=None, models=None, batch_size=16):
     encoder.to(device).eval()
     decoder.to(device).eval()
     split_dir = os.path.join(getattr(opt, "splits_dir", "splits"), opt.eval_split)
+    syns = opt.eval_split == "SYNS"
     if dataloader is None:
         filenames = datasets.readlines(os.path.join(split_dir, "test_files.txt"))
-        ds = datasets.KITTIRAWDataset(filenames, 0, height, width, kt_path=opt.kt_path, is_train=False, kt=True,
-                                      naive_mix=True)
+        if syns:                                         # evaluate_depth.py:128-132
+            ds = datasets.SYNSRAWDataset(filenames, 0, height, width, syns_path=opt.syns_path, is_train=False,
+                                         naive_mix=True)
+        else:
+            ds = datasets.KITTIRAWDataset(filenames, 0, height, width, kt_path=opt.kt_path, is_train=False, kt=True,
+                                          naive_mix=True)
         dataloader = datasets.DeviceLoader(ds, batch_size, datasets.DeviceCollate(height, width, [0], device),
                                            shuffle=False, drop_last=False, num_workers=getattr(opt, "num_workers", 8))
+    if syns:
+        return _evaluate_syns(opt, dataloader, gt_depths, gt_edges, inv_K, encoder, decoder, split_dir, device)
     gt_path = os.path.join(split_dir, "gt_depths.npz")
     if gt_depths is None and not os.path.isfile(gt_path) and opt.eval_split in ("eigen", "eigen_zhou"):
         # what export_gt_depth.py would have written, straight into the device buffer the metrics read
@@ -176,4 +363,49 @@ def evaluate(opt, dataloader=None, gt_depths=None, models=None, batch_size=16):
         print(" Scaling ratios | med: {:0.3f} | std: {:0.3f}".format(med, np.std(ratios / med)))
     print("\n  " + ("{:>8} | " * 7).format("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3"))
     print(("&{: 8.3f}  " * 7).format(*mean_errors.tolist()) + "\\\\")
+    return mean_errors, ratios
+
+
+def _evaluate_syns(opt, dataloader, gt_depths, gt_edges, inv_K, encoder, decoder, split_dir, device):
+    """evaluate_depth.py with `--eval_split SYNS [--chamfer]`: every batch is scored while it is in HBM; the rows are
+    read back once, at the end."""
+    import os
+    from . import datasets
+    from .layers import disp_to_depth
+    if gt_depths is None:
+        gt_depths = np.load(os.path.join(split_dir, "gt_depths.npz"), fix_imports=True, encoding="latin1",
+                            allow_pickle=True)["data"]
+    if gt_edges is None and not isinstance(gt_depths, GroundTruthSet):
+        gt_edges = np.load(os.path.join(split_dir, "gt_edges.npz"), fix_imports=True, encoding="latin1",
+                           allow_pickle=True)["data"]
+    gts = gt_depths if isinstance(gt_depths, GroundTruthSet) else GroundTruthSet(gt_depths, device, crop=False,
+                                                                                 edges=gt_edges)
+    chamfer = bool(getattr(opt, "chamfer", False))
+    if chamfer and inv_K is None:
+        inv_K = datasets.SYNSRAWDataset.load_intrinsic_syns()[1]
+    median_scaling = not opt.disable_median_scaling
+    scale = opt.pred_depth_scale_factor
+    if opt.eval_stereo:
+        median_scaling, scale = False, STEREO_SCALE_FACTOR
+    out, ratio_rows, first = [], [], 0
+    with torch.no_grad():
+        for data in dataloader:
+            pred_disp, _ = disp_to_depth(decoder(encoder(data[("color", 0, 0)]))[("disp", 0)], opt.min_depth, opt.max_depth)
+            n = pred_disp.shape[0]
+            res, rows = syns_metrics(pred_disp, gts, list(range(first, first + n)), inv_K=inv_K, chamfer=chamfer,
+                                     mode="evaluate", median_scaling=median_scaling, scale_factor=scale,
+                                     return_rows=True)
+            out.append(res)
+            ratio_rows.append(rows[:, 7])
+            first += n
+    out = torch.cat(out).cpu().numpy()                                  # the only host synchronisation
+    ratios = torch.cat(ratio_rows).cpu().numpy().astype(np.float64) if median_scaling else None
+    assert first == len(gts), "split has %d images, ground truth %d" % (first, len(gts))
+    ncol = 9 if chamfer else 7
+    mean_errors = out[:, :ncol].mean(0)
+    if median_scaling:
+        med = np.median(ratios)
+        print(" Scaling ratios | med: {:0.3f} | std: {:0.3f}".format(med, np.std(ratios / med)))
+    print("\n  " + ("{:>8} | " * ncol).format(*SYNS_COLUMNS[:ncol]))
+    print(("&{: 8.3f}  " * ncol).format(*mean_errors.tolist()) + "\\\\")
     return mean_errors, ratios

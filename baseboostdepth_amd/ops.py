@@ -1606,3 +1606,22 @@ def velo_depth(points, counts, proj, shapes, out=None, offsets=None, vel_depth=F
     backend.run("bbd_velo_depth", out, ptr(points), ptr(desc), ptr(proj), ptr(scratch), n_ints, ptr(out), n,
                 int(max(counts)), _lib.VELO_VEL_DEPTH if vel_depth else 0)
     return out, list(offsets)
+
+
+# ---------------------------------------------------------------------------- all-pairs nearest neighbour
+def chamfer_nn(a, b, backend=None):
+    """Squared distance of every point to its nearest neighbour in the other set, both ways, in ONE `bbd_chamfer_nn`
+    call: a [Na,3], b [Nb,3] float32 -> (nn_a [Na], nn_b [Nb]) float32 with nn_a[i] = min_j |a_i - b_j|^2 and
+    nn_b[j] = min_i |a_i - b_j|^2.  The distance is (dx*dx + dy*dy) + dz*dz from the differences, so the result is
+    defined to the bit; +inf where the other set is empty.  What the reference's `ChamferDistance()` extension
+    returns as its first two outputs (evaluate_depth.py:83)."""
+    backend = backend or default_backend()
+    a, b = a.detach(), b.detach()
+    assert a.dim() == 2 and a.shape[1] == 3 and b.dim() == 2 and b.shape[1] == 3
+    assert a.dtype == torch.float32 and b.dtype == torch.float32 and a.device == b.device
+    a, b = a.contiguous(), b.contiguous()
+    backend._check(a, b)
+    nn_a = torch.empty(a.shape[0], dtype=torch.float32, device=a.device)
+    nn_b = torch.empty(b.shape[0], dtype=torch.float32, device=a.device)
+    backend.run("bbd_chamfer_nn", a, ptr(a), ptr(b), a.shape[0], b.shape[0], ptr(nn_a), ptr(nn_b))
+    return nn_a, nn_b

@@ -58,7 +58,7 @@ _FLAGS = [
     ("--early_pose_rows", dict(type=str, default="0")),
 ]
 # other zoos / datasets of the reference: parsed, refused when set
-_OUT_OF_SCOPE = ["--SYNS_eval", "--SQL", "--SQL_L", "--CA_depth", "--DIFFNet", "--chamfer", "--stereo_guide",
+_OUT_OF_SCOPE = ["--SYNS_eval", "--SQL", "--SQL_L", "--CA_depth", "--DIFFNet", "--stereo_guide",
                  "--x_min", "--png", "--use_stereo", "--eval_eigen_to_benchmark"]
 
 
@@ -70,6 +70,8 @@ class MonodepthOptions:
         for flag in _OUT_OF_SCOPE:
             self.parser.add_argument(flag, action="store_true", help="not part of this build")
         self.parser.add_argument("--debug", action="store_true")
+        self.parser.add_argument("--chamfer", action="store_true",
+                                 help="with --eval_split SYNS: also the point-cloud F-score and IoU")
         self.parser.add_argument("--syns_path", type=str, default="data/KITTI_RAW")
         self.parser.add_argument("--x_val", type=int, default=3)
 

@@ -1071,7 +1071,7 @@ class Trainer:
         summed, as `accumulate=True` does over the reference's loop.  Values stay on the device
         (0-dim tensors) so the validation loop never synchronises per image."""
         if SYNS:
-            raise NotImplementedError("SYNS edge metrics (cv2/scipy host code, trainer.py:577-593) are out of scope")
+            return self._compute_edge_losses(outputs, losses, idx, accumulate)
         from .evaluation import depth_metrics, GroundTruthSet
         if not isinstance(self.gt_depths, GroundTruthSet):
             self.set_ground_truth(self.gt_depths)
@@ -1081,6 +1081,50 @@ class Trainer:
         for k, name in enumerate(self.depth_metric_names):
             losses[name] = losses[name] + sums[k] if accumulate and name in losses else sums[k]
         return losses
+
+    # ------------------------------------------------------------------ SYNS-Patches edge metrics (trainer.py:576-594)
+    depth_metric_names_syns = ["edge_Acc", "edge_comp"]                    # trainer.py:137
+
+    def set_ground_truth_syns(self, gt_depths, gt_edges):
+        """Packs the SYNS-Patches validation ground truth (the reference's `self.gt_depth_syns` / `self.gt_edges_syns`,
+        `splits/SYNS/val/{gt_depths,gt_edges}.npz`) into device memory once: depth maps and, at the same offsets, the
+        edge maps as bytes.  No crop window: SYNS is scored on the whole image."""
+        from .evaluation import GroundTruthSet
+        self.gt_syns = GroundTruthSet(gt_depths, self.device, crop=False, edges=gt_edges)
+        return self.gt_syns
+
+    def _compute_edge_losses(self, outputs, losses, idx, accumulate):
+        """`compute_depth_losses(SYNS=True)`: the depth prediction resized to the ground-truth size and clamped to
+        [1e-3, 80], its log-depth edges (blur, Sobel, magnitude above its mean), the distance transforms and the two
+        means of layers.compute_depth_errors(SYNS=True) - all on the device (bbd_syns.hip); `edge_Acc` / `edge_comp`
+        are 0-dim device tensors, summed over a batched prediction as `accumulate=True` sums over the reference's
+        batch-1 loop."""
+        from .evaluation import syns_metrics
+        if getattr(self, "gt_syns", None) is None:
+            raise RuntimeError("call set_ground_truth_syns(gt_depths, gt_edges) before compute_depth_losses(SYNS=True)")
+        indices = [int(idx)] if not hasattr(idx, "__len__") else [int(i) for i in idx]
+        rows = syns_metrics(outputs["depth", 0, 0], self.gt_syns, indices, mode="trainer", backend=self._backend())
+        sums = rows[:, 5:7].sum(0)
+        for k, name in enumerate(self.depth_metric_names_syns):
+            losses[name] = losses[name] + sums[k] if accumulate and name in losses else sums[k]
+        return losses
+
+    def val_syns(self, val_loader):
+        """The SYNS half of the reference's validation pass (trainer.py:644-663): mean `edge_Acc` / `edge_comp` over
+        the loader's images; keeps `self.best_syns` (edge_comp, initially 100).  One host synchronisation, at the end."""
+        self.set_eval()
+        losses, images = {}, 0
+        with torch.no_grad():
+            for batch_idx, inputs in enumerate(val_loader):
+                outputs, _ = self.process_batch(inputs, batch_idx, is_train=False)
+                n = outputs["depth", 0, 0].shape[0]
+                self.compute_depth_losses(outputs, losses, list(range(images, images + n)), SYNS=True, accumulate=True)
+                images += n
+        result = {name: float(losses[name]) / max(images, 1) for name in self.depth_metric_names_syns}
+        if result["edge_comp"] < getattr(self, "best_syns", 100.0):
+            self.best_syns = result["edge_comp"]
+        self.set_train()
+        return result
 
     def val(self, val_loader, is_init=None):
         """Validation pass (trainer.py:623-665): mean of the seven metrics over the loader's images;

@@ -35,8 +35,9 @@ extern "C" {
  * 6 = round 5: bbd_bn_act_grouped_fwd gained `untracked_groups` (the padding group of the batched pose pass);
  * 7 = round 6: bbd_bn_act_grouped_dev_fwd / _bwd (group table resident on the device: launches whose arguments do not
  * depend on the batch signature); 8 = bbd_disp_viz / bbd_disp_viz_scratch_ints (single-image prediction);
- * 9 = bbd_velo_depth / bbd_velo_depth_scratch_ints (ground-truth depth maps from Velodyne scans). */
-#define BBD_ABI_VERSION 9
+ * 9 = bbd_velo_depth / bbd_velo_depth_scratch_ints (ground-truth depth maps from Velodyne scans);
+ * 10 = bbd_syns_* / bbd_chamfer_nn (SYNS-Patches evaluation: edge and point-cloud metrics). */
+#define BBD_ABI_VERSION 10
 
 /* Source frames live in separate tensors, one per frame id (inputs[("color", f, 0)],
  * trainer.py:428).  A "slot" indexes a host array of their base pointers. */
@@ -337,6 +338,64 @@ int bbd_disp_viz(const float* disp, const int32_t* desc, const uint8_t* lut, uin
 int bbd_velo_depth_scratch_ints(int total_pixels, int n_frames);
 int bbd_velo_depth(const float* points, const int32_t* desc, const double* proj, int32_t* scratch, int scratch_ints,
                    float* out, int n_frames, int max_points, int flags, void* stream);
+
+/* ---- SYNS-Patches evaluation (evaluate_depth.py:26-102, :244-297; trainer.py:576-594): edge accuracy and
+ * completeness, `err`, point-cloud F-score and IoU, for a ragged batch of n images per call.  Images are described by
+ * the BBD_EVAL_DESC table of bbd_depth_metrics (the crop window is not used: SYNS is scored on the whole image); the
+ * ground-truth edge maps are bytes (non-zero = edge) in a buffer with the SAME element offsets as the depth maps.
+ * Per-image work arrays (edge maps, distance maps, scratch) are strided: image i at base + i * px_stride elements,
+ * px_stride a multiple of 4 and >= max_h * max_w, max_h / max_w >= every GH / GW of the batch (they size the launch;
+ * an image that does not fit px_stride is skipped).  scratch holds bbd_syns_scratch_ints(n, px_stride) int32, 16-byte
+ * aligned; every entry uses it from its start, so one buffer serves the calls of a batch one after another.  The
+ * arithmetic, operation by operation, is in bbd_syns_math.h (and bbd_eval_math.h for the resampled prediction);
+ * everything is compiled with -ffp-contract=off.  No result depends on launch geometry or atomic order: sums are
+ * integer or fp64 in an order the kernels fix, minima are over integers or over float32 values.
+ *
+ * bbd_syns_pred_edges: d = the prediction at every ground-truth pixel (flags 0: depth, F.interpolate bilinear then
+ *   clamp to [clamp_lo, clamp_hi]; BBD_EVAL_PRED_IS_DISP: disparity, cv2-style linear resize, then 1 / x, unclamped),
+ *     L   = (d > 0) * float32(log(double(max(d, 2^-23))))
+ *     B   = GaussianBlur 3x3 sigma 1 of L in float32, BORDER_REFLECT_101: horizontal then vertical pass, each
+ *           k1 * (a + c) + k0 * b with k = float32(exp(-x^2/2) / sum)
+ *     mag = sqrt(dx^2 + dy^2), dx / dy the 5x5 Sobel of B in float64 (smoothing 1 4 6 4 1, derivative -1 -2 0 2 1)
+ *     edge[i * px_stride + p] = mag > mean(mag)  (one byte, 0 / 1);  stats[i] = {mean(mag), number of edge pixels}.
+ * bbd_syns_edt: out = SQUARED exact Euclidean distance of every pixel to the nearest non-zero byte of `map` (what
+ *   scipy.ndimage.distance_transform_edt(1 - map) ** 2 gives), int32; BBD_SYNS_EDT_NONE (2^30) where the map has no
+ *   non-zero byte.  Sizes with max_w > 8192, max_h >= 32768 or max_h^2 + max_w^2 >= 2^30 return BBD_E_TOOMANY.
+ * bbd_syns_edge_metrics: with valid = min_depth < gt < max_depth, tgt = valid & gt_edge, D_t / D_p the distances to
+ *   tgt / pred_edge (square roots in fp64), near = pred_edge & (D_t < th):
+ *     out[i] = {edge_Acc = mean(D_t[near]), edge_comp = mean(D_p[tgt]), err = mean |p - gt| over valid,
+ *               count(near), count(tgt), count(valid), count(pred_edge), 0}            (BBD_SYNS_OUT doubles)
+ *   edge_Acc = edge_comp = th when near is empty, NaN when tgt is empty (scipy's input then has no background pixel).
+ *   p = the prediction resampled as in bbd_depth_metrics (times scale_factor in disparity mode), times rows[i][7]
+ *   (the median-scaling ratio of the bbd_depth_metrics row, read on the device) unless BBD_EVAL_NO_MEDIAN_SCALING,
+ *   clamped to [min_depth, max_depth].
+ * bbd_chamfer_nn: nn_a[i] = min_j |a_i - b_j|^2, nn_b[j] = min_i |a_i - b_j|^2 for a [na,3], b [nb,3] float32,
+ *   d = (dx*dx + dy*dy) + dz*dz from the differences: defined to the bit; +inf where the other set is empty.
+ * bbd_syns_pointcloud: pred_org = clamp(rows[i][7] * prediction, min_depth, max_depth), gt_org = gt; flat pixel k of
+ *   every valid pixel becomes depth * ((iK[j][0] * u + iK[j][1] * v) + iK[j][2]), (u, v) = (k / GH, k % GH) - the
+ *   reference's own pairing (torch.meshgrid(arange(w), arange(h)) in ij order against a row-major depth map) - or
+ *   (k % GW, k / GW) with BBD_SYNS_RAYS_PIXEL; nearest neighbours both ways as bbd_chamfer_nn;
+ *     P = count(sqrtf(nn_p) < th) / N, R likewise over nn_t, float32;  P, R < 1e-3: f = iou = P, else
+ *     f = 2PR / (P + R), iou = PR / (P + R - PR);  out[i] = {f, iou, P, R, count_p, count_t, N, 0}. */
+#define BBD_SYNS_OUT 8
+#define BBD_SYNS_CLOUD_OUT 8
+#define BBD_SYNS_RAYS_PIXEL 8
+int bbd_syns_scratch_ints(int n, int px_stride);
+int bbd_syns_pred_edges(const float* pred, const int32_t* desc, int32_t* scratch, int scratch_ints, uint8_t* edge,
+                        double* stats, int n, int h, int w, int px_stride, int max_h, int max_w, double clamp_lo,
+                        double clamp_hi, int flags, void* stream);
+int bbd_syns_edt(const uint8_t* map, const int32_t* desc, int32_t* out, int n, int px_stride, int max_h, int max_w,
+                 void* stream);
+int bbd_syns_edge_metrics(const float* pred, const float* gt, const uint8_t* gt_edge, const uint8_t* pred_edge,
+                          const int32_t* desc, const float* rows, int32_t* scratch, int scratch_ints, double* out,
+                          int n, int h, int w, int px_stride, int max_h, int max_w, double min_depth,
+                          double max_depth, double clamp_lo, double clamp_hi, double scale_factor, double th,
+                          int flags, void* stream);
+int bbd_chamfer_nn(const float* a, const float* b, int na, int nb, float* nn_a, float* nn_b, void* stream);
+int bbd_syns_pointcloud(const float* pred, const float* gt, const int32_t* desc, const float* rows,
+                        const float* inv_K, int32_t* scratch, int scratch_ints, float* out, int n, int h, int w,
+                        int px_stride, int max_h, int max_w, double min_depth, double max_depth, double clamp_lo,
+                        double clamp_hi, double th, int flags, void* stream);
 
 /* ---- Loader image pipeline: replaces the per-item Pillow/torchvision work of
  * datasets/mono_dataset.py:186-205 (Resize(LANCZOS) chain, ColorJitter, ToTensor) and the stacking of
