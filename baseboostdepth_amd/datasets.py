@@ -231,6 +231,82 @@ class SYNSRAWDataset(MonoDataset):
         return os.path.join(self.syns_path, "images", folder, "{}.png".format(frame_index))
 
 
+class KITTIOdomDataset(KITTIDataset):
+    """KITTI odometry sequences, evaluation items only (kitti_dataset.py:62-93).  Split lines are `sequence frame side`, the
+    image is `<odom_path>/sequences/<NN>/image_<2|3>/data/<%06d>.jpg`; `odom_path` defaults to `dirname(kt_path)/odom`,
+    which is what the reference computes from its `kt_path`.
+
+    One item is ONE frame, in the form `DeviceCollate` / `DeviceLoader` take.  The reference's item decodes and resizes
+    the line's frame and its seven successors and the pose evaluation uses three of them (mono_dataset.py:160-176);
+    here `windows(skip)` names every frame the evaluation needs once, and the windows are index pairs into that list."""
+
+    def __init__(self, *args, odom_path=None, **kwargs):
+        super().__init__(*args, **kwargs)
+        if self.is_train:
+            raise ValueError("the odometry sequences are served for evaluation only: there are no training items")
+        if odom_path is None and self.kt_path is None:
+            raise ValueError("KITTIOdomDataset needs odom_path or kt_path (odom_path defaults to dirname(kt_path)/odom)")
+        self.odom_path = odom_path if odom_path is not None else os.path.join(os.path.dirname(self.kt_path), "odom")
+
+    def get_image_path_odom(self, data_path, folder, frame_index, side):
+        """kitti_dataset.py:68-74; `data_path` is ignored: the sequences live under `odom_path`."""
+        return os.path.join(self.odom_path, "sequences/{:02d}".format(int(folder)),
+                            "image_{}".format({"r": "3", "l": "2"}[side]), "data",
+                            "{:06d}{}".format(frame_index, self.img_ext))
+
+    def get_image_path_kt(self, data_path, frame_index, side, folder):
+        return self.get_image_path_odom(data_path, folder, frame_index, side)
+
+    def index_to_folder_and_frame_idx(self, index):
+        """kitti_dataset.py:76-87."""
+        return self.index_to_folder_and_frame_idx_kt(index)
+
+    def windows(self, skip=2):
+        """The windows of evaluate_pose.py:85-116 as tables: returns (frames, pairs, N).
+
+        `frames`: split lines (`sequence frame side`), every frame some window reads, once, in order of first use -
+        `KITTIOdomDataset(frames, ...)` is the dataset whose items fill the frame pool.  `pairs`: int32 [1 + skip, N, 2] of
+        indices into it: section 0 = (frame, frame + skip) of window i, the direct pose's input; section 1 + k =
+        (frame + k, frame + k + 1), the k-th single step.  N: the number of windows kept.
+
+        A line whose window runs past the last frame on disk is dropped, which is what the reference's trailing
+        `except: print('passed')` does.  A frame missing before that raises FileNotFoundError: the reference would skip
+        the window and score every later prediction against the ground truth of another frame."""
+        S = int(skip)
+        if S < 1:
+            raise ValueError("skip must be at least 1, got %d" % S)
+        lines = [self.index_to_folder_and_frame_idx(i) for i in range(len(self))]
+        for line, (folder, t, side) in zip(self.filenames, lines):
+            if side not in ("l", "r"):
+                raise ValueError("odometry split line %r: expected `sequence frame side`" % line)
+
+        def path(folder, t, side):
+            return self.get_image_path_odom(self.kt_path, folder, t, side)
+
+        last = {}                       # (sequence, side) -> last frame on disk among those a window reads
+        for folder, t, side in lines:
+            for f in range(t, t + S + 1):
+                if f > last.get((folder, side), -1) and self._exists(path(folder, f, side)):
+                    last[(folder, side)] = f
+        pool, pairs, dropped = {}, [], None
+        for line, (folder, t, side) in zip(self.filenames, lines):
+            missing = [f for f in range(t, t + S + 1) if not self._exists(path(folder, f, side))]
+            if missing and missing[0] < last.get((folder, side), -1):
+                raise FileNotFoundError("%s is missing in the middle of sequence %s (later frames exist)"
+                                        % (path(folder, missing[0], side), folder))
+            if missing:
+                dropped = dropped or (line, path(folder, missing[0], side))
+                continue
+            if dropped is not None:
+                raise FileNotFoundError("%s is missing for split line %r but later lines are complete: the windows "
+                                        "after it would be scored against the wrong ground truth" % (dropped[1], dropped[0]))
+            idx = [pool.setdefault((folder, f, side), len(pool)) for f in range(t, t + S + 1)]
+            pairs.append([(idx[0], idx[S])] + [(idx[k], idx[k + 1]) for k in range(S)])
+        frames = ["%s %d %s" % key for key in pool]
+        table = np.asarray(pairs, dtype=np.int32).reshape(len(pairs), 1 + S, 2).transpose(1, 0, 2)
+        return frames, np.ascontiguousarray(table), len(pairs)
+
+
 class FrameCache:
     """Decoded frames kept resident in HBM (uint8 HWC, as decoded).
 

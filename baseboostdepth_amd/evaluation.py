@@ -11,7 +11,12 @@ The SYNS-Patches metrics (evaluate_depth.py:26-102 with `--eval_split SYNS [--ch
 layer callable on its own: `pred_edges` (log, blur, Sobel, threshold), `distance_transform` (exact squared Euclidean
 distance maps), `edge_metrics` (edge accuracy / completeness and `err`), `pointcloud_metrics` (F-score and IoU of the
 back-projected clouds, all-pairs nearest neighbour) and `syns_metrics`, the reference's 9-column row.
+
+The KITTI odometry evaluation (evaluate_pose.py) is `pose_ate` - chained poses, local ground truth, the trajectory error
+of every track and its mean / std in one `bbd_pose_ate` call - and `evaluate_pose`, the evaluator above it.
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -409,3 +414,170 @@ def _evaluate_syns(opt, dataloader, gt_depths, gt_edges, inv_K, encoder, decoder
     print("\n  " + ("{:>8} | " * ncol).format(*SYNS_COLUMNS[:ncol]))
     print(("&{: 8.3f}  " * ncol).format(*mean_errors.tolist()) + "\\\\")
     return mean_errors, ratios
+
+
+# ---------------------------------------------------------------------------- KITTI odometry (evaluate_pose.py)
+PoseATE = collections.namedtuple("PoseATE", "direct chained gt_local ates summary")
+PoseATE.__doc__ = """Result of `pose_ate`, device tensors: `direct` float32 [N,4,4] (= poses[0]), `chained` float32 [N,4,4],
+`gt_local` float64 [M-S,4,4], `ates` float64 [2,N-S] (row 0 direct, row 1 chained), `summary` float64 [2,4] (mean,
+population std, count, 0 per row)."""
+
+
+def read_poses_file(path):
+    """A KITTI odometry poses file as float64 [M, 12] (evaluate_pose.py:125, before its reshape)."""
+    return np.loadtxt(path, dtype=np.float64, ndmin=2).reshape(-1, 12)
+
+
+def pose_ate(poses, gt_global, skip=2, track_length=1, backend=None):
+    """evaluate_pose.py:101-116 and :125-162 after the pose network, in ONE `bbd_pose_ate` call (three small launches, no
+    host synchronisation): `poses` float32 [1+S, N, 4, 4] (or [1+S, N, 16]) holds, for window i, the direct pose of frames
+    (i, i+S) in section 0 and the single-step pose of frames (i+k, i+k+1) in section 1+k; `gt_global` [M, 12] (or
+    [M, 3, 4]) float64 are the rows of the sequence's poses file.  Returns a `PoseATE`.  Track i of [0, N-S) scores
+    min(track_length, N-i) poses like Python's slices; a track whose predicted translations are all zero is NaN (0/0)
+    and makes the mean and std of its row NaN, as in numpy."""
+    backend = backend or ops.default_backend()
+    S, L = int(skip), int(track_length)
+    if S < 1 or L < 1:
+        raise ValueError("pose_ate: skip and track_length must be at least 1 (got %d, %d)" % (S, L))
+    poses = poses.detach()
+    if poses.dtype != torch.float32 or poses.dim() not in (3, 4) or poses.shape[0] != 1 + S \
+            or tuple(poses.shape[2:]) not in ((16,), (4, 4)):
+        raise ValueError("pose_ate: poses must be float32 [1 + skip = %d, N, 4, 4], got %s %s"
+                         % (1 + S, poses.dtype, tuple(poses.shape)))
+    dev = poses.device
+    N = poses.shape[1]
+    poses = poses.reshape(1 + S, N, 16).contiguous()
+    gt = torch.as_tensor(gt_global, dtype=torch.float64).reshape(-1, 12)
+    M = gt.shape[0]
+    if N > M - S:
+        raise ValueError("pose_ate: %d windows of skip %d need %d ground-truth poses, the sequence has %d (N = %d > "
+                         "M - S = %d)" % (N, S, N + S, M, N, M - S))
+    if gt.device != dev:
+        gt = (gt.pin_memory() if dev.type == "cuda" else gt).to(dev, non_blocking=True)
+    gt = gt.contiguous()
+    backend._check(poses, gt)
+    tracks = max(N - S, 0)
+    chained = torch.empty(N, 4, 4, dtype=torch.float32, device=dev)
+    gt_local = torch.empty(M - S, 4, 4, dtype=torch.float64, device=dev)
+    ates = torch.empty(2, tracks, dtype=torch.float64, device=dev)
+    summary = torch.empty(2, 4, dtype=torch.float64, device=dev)
+    pose_ate_into(poses, gt, chained, gt_local, ates, summary, S, L, backend)
+    return PoseATE(poses[0].view(N, 4, 4), chained, gt_local, ates, summary)
+
+
+def pose_ate_into(poses, gt, chained, gt_local, ates, summary, skip, track_length, backend=None):
+    """The `bbd_pose_ate` call itself on caller-owned, contiguous tensors of one device (shapes as `pose_ate` builds
+    them); every element of the four outputs is written, nothing else is."""
+    backend = backend or ops.default_backend()
+    N, M = poses.shape[1], gt.shape[0]
+    assert chained.numel() == N * 16 and gt_local.numel() == (M - skip) * 16 and summary.numel() == 8
+    assert ates.numel() == 2 * max(N - skip, 0)
+    backend._check(poses, gt, chained, gt_local, ates, summary)
+    backend.run("bbd_pose_ate", summary, ptr(poses), ptr(gt), ptr(chained), ptr(gt_local), ptr(ates), ptr(summary),
+                N, M, int(skip), int(track_length))
+
+
+def odom_sequence(eval_split):
+    """`odom_<n>` -> n (evaluate_pose.py:50-53; every sequence with ground truth, 0-10, is accepted)."""
+    parts = str(eval_split).split("_")
+    if len(parts) != 2 or parts[0] != "odom" or not parts[1].isdigit() or not 0 <= int(parts[1]) <= 10:
+        raise ValueError("eval_split should be odom_0 ... odom_10, got %r" % (eval_split,))
+    return int(parts[1])
+
+
+def odom_paths(opt):
+    """(sequence, split file, odometry root, poses file) of `opt` (evaluate_pose.py:53-57, :124, kitti_dataset.py:71)."""
+    import os
+    seq = odom_sequence(opt.eval_split)
+    root = getattr(opt, "odom_path", None)
+    if root is None:
+        root = os.path.join(os.path.dirname(opt.kt_path), "odom")
+    return (seq, os.path.join(getattr(opt, "splits_dir", "splits"), "odom", "test_files_{:02d}.txt".format(seq)), root,
+            os.path.join(root, "poses", "{:02d}.txt".format(seq)))
+
+
+def evaluate_pose(opt, dataloader=None, gt_poses=None, models=None, batch_windows=64):
+    """The reference's `evaluate_pose.py`: the pose network's direct `skip_frame`-step pose and the pose chained from its
+    single steps, scored against KITTI odometry ground truth (absolute trajectory error over `track_length`-pose tracks).
+    Prints the reference's two `Trajectory error` lines, direct first, and returns a dict: `ate_mean`, `ate_std`,
+    `ate_chained_mean`, `ate_chained_std`, `ates` (numpy [2, N-S]), `pred_poses`, `pred_poses_chained` (numpy [N,4,4]).
+
+    Every frame is decoded and resized once into a pool [F,3,H,W] by the device loader; per chunk of `batch_windows`
+    windows the 1+S pair sections are gathered (`ops.gather_pairs`) and go through the pose network as ONE batch, the
+    matrices (`ops.pose_matrix`) land in a persistent [1+S, N, 16] buffer, and after the last chunk one `pose_ate` call
+    scores all windows; the finished table is read back once.  (The reference decodes 8 frames per window, runs the
+    network three times at batch 1, copies every pose to the host and scores in a Python loop.)
+
+    `dataloader` / `gt_poses` / `models` may be injected.  The dataloader must yield the frames `windows(skip)` of the
+    split's `KITTIOdomDataset` names, in that order, as `("color", 0, 0)`; by default the split is
+    `opt.splits_dir/odom/test_files_<nn>.txt`, frames and `poses/<nn>.txt` come from `opt.odom_path` (default
+    `dirname(opt.kt_path)/odom`) and weights from `pose_encoder.pth` / `pose.pth` in `opt.load_weights_folder`.
+    Departures from the reference, both deliberate: only TRAILING windows without frames are dropped (a frame missing
+    in the middle raises), and the input size is `opt.height x opt.width` (the reference fixes 192 x 640, the defaults)."""
+    import os
+    from . import datasets, networks, tuning
+    tuning.use_shipped_db()
+    seq, split_file, odom_root, poses_file = odom_paths(opt)
+    S, L = int(getattr(opt, "skip_frame", 2)), int(getattr(opt, "track_length", 1))
+    device = torch.device("cuda:%d" % getattr(opt, "cuda", 0))
+    height, width = opt.height, opt.width
+    # ---- host: the window tables and the ground truth, checked before anything is launched
+    lines = datasets.KITTIOdomDataset(datasets.readlines(split_file), 0, height, width, kt_path=opt.kt_path, is_train=False,
+                                      kt=True, naive_mix=True, odom_path=odom_root)
+    frames, pairs, N = lines.windows(S)
+    if gt_poses is None:
+        gt_poses = read_poses_file(poses_file)
+    gt_poses = torch.as_tensor(gt_poses, dtype=torch.float64).reshape(-1, 12)
+    M = gt_poses.shape[0]
+    if N > M - S:
+        raise ValueError("evaluate_pose: the split has N = %d windows of skip %d but the ground truth has %d poses "
+                         "(M - S = %d)" % (N, S, M, M - S))
+    if models is None:
+        folder = os.path.expanduser(opt.load_weights_folder)
+        assert os.path.isdir(folder), "Cannot find a folder at {}".format(folder)
+        encoder = networks.ResnetEncoder(opt.num_layers, False, 2)
+        encoder.load_state_dict(torch.load(os.path.join(folder, "pose_encoder.pth"), map_location=device))
+        decoder = networks.PoseDecoder(encoder.num_ch_enc, 1, 2)
+        decoder.load_state_dict(torch.load(os.path.join(folder, "pose.pth"), map_location=device))
+    else:
+        encoder, decoder = models
+    encoder.to(device).eval()
+    decoder.to(device).eval()
+    if dataloader is None:
+        pool_set = datasets.KITTIOdomDataset(frames, 0, height, width, kt_path=opt.kt_path, is_train=False, kt=True,
+                                             naive_mix=True, odom_path=odom_root)
+        dataloader = datasets.DeviceLoader(pool_set, 32, datasets.DeviceCollate(height, width, [0], device), shuffle=False,
+                                           drop_last=False, num_workers=getattr(opt, "num_workers", 8))
+    print("-> Computing pose predictions")
+    F = len(frames)
+    pool = torch.empty(F, 3, height, width, device=device)
+    first = 0
+    for data in dataloader:                              # each frame resized once, straight into the pool
+        color = data[("color", 0, 0)]
+        assert first + color.shape[0] <= F, "the dataloader yields more than the %d frames of the windows" % F
+        pool[first:first + color.shape[0]].copy_(color)
+        first += color.shape[0]
+    assert first == F, "the windows need %d frames, the dataloader gave %d" % (F, first)
+    # [2, 1+S, N]: first and second frame of every pair, each plane contiguous
+    table = torch.from_numpy(np.ascontiguousarray(pairs.transpose(2, 0, 1))).pin_memory().to(device, non_blocking=True)
+    poses = torch.empty(1 + S, N, 16, device=device)
+    with torch.no_grad():
+        for lo in range(0, N, max(1, int(batch_windows))):
+            chunk = table[:, :, lo:lo + batch_windows]
+            n = chunk.shape[2]
+            x = ops.gather_pairs(pool, chunk[0].reshape(-1), chunk[1].reshape(-1))               # [(1+S) n, 6, H, W]
+            axisangle, translation = decoder([encoder(x)])
+            mats = ops.pose_matrix(axisangle[:, 0], translation[:, 0])
+            poses[:, lo:lo + n] = mats.view(1 + S, n, 16)
+        res = pose_ate(poses, gt_poses, skip=S, track_length=L)
+        packed = torch.cat([res.summary.reshape(-1), res.ates.reshape(-1), res.direct.reshape(-1).double(),
+                            res.chained.reshape(-1).double()])               # float32 -> float64 and back is exact
+    host = packed.cpu().numpy()                          # the only host synchronisation: the finished tables
+    tracks = res.ates.shape[1]
+    summary, ates = host[:8].reshape(2, 4), host[8:8 + 2 * tracks].reshape(2, tracks)
+    mats = host[8 + 2 * tracks:].astype(np.float32).reshape(2, N, 4, 4)
+    out = {"ate_mean": float(summary[0, 0]), "ate_std": float(summary[0, 1]), "ate_chained_mean": float(summary[1, 0]),
+           "ate_chained_std": float(summary[1, 1]), "ates": ates, "pred_poses": mats[0], "pred_poses_chained": mats[1]}
+    print("\n   Trajectory error: {:0.3f}, std: {:0.3f}\n".format(out["ate_mean"], out["ate_std"]))
+    print("\n   Trajectory error: {:0.3f}, std: {:0.3f}\n".format(out["ate_chained_mean"], out["ate_chained_std"]))
+    return out

@@ -496,10 +496,11 @@ def gather_pairs(pool, idx_a, idx_b, normalize=None, backend=None):
     R = idx_a.numel()
     assert pool.is_contiguous() and idx_a.dtype == torch.int32 and idx_b.dtype == torch.int32 and idx_b.numel() == R
     backend._check(pool, idx_a, idx_b)
+    idx_a, idx_b = idx_a.contiguous(), idx_b.contiguous()        # held until the launch: a temporary's memory is reused at once
     out = torch.empty(R, 2 * C, H, W, device=pool.device, dtype=torch.float32)
     sub, mul = (0.0, 1.0) if normalize is None else (float(np.float32(normalize[0])),
                                                      float(np.float32(1.0) / np.float32(normalize[1])))
-    backend.run("bbd_gather_pairs", pool, ptr(pool), ptr(idx_a.contiguous()), ptr(idx_b.contiguous()), ptr(out), R, C * H * W, sub, mul)
+    backend.run("bbd_gather_pairs", pool, ptr(pool), ptr(idx_a), ptr(idx_b), ptr(out), R, C * H * W, sub, mul)
     return out
 
 

@@ -74,6 +74,12 @@ class MonodepthOptions:
                                  help="with --eval_split SYNS: also the point-cloud F-score and IoU")
         self.parser.add_argument("--syns_path", type=str, default="data/KITTI_RAW")
         self.parser.add_argument("--x_val", type=int, default=3)
+        # evaluate_pose.py (--eval_split odom_<n>): the KITTI odometry tree (default: `odom` next to --kt_path, where the
+        # reference's loader looks), and the two constants the reference hard-codes
+        self.parser.add_argument("--odom_path", type=str, default=None,
+                                 help="KITTI odometry root (sequences/, poses/); default dirname(kt_path)/odom")
+        self.parser.add_argument("--skip_frame", type=int, default=2)
+        self.parser.add_argument("--track_length", type=int, default=1)
 
     def parse(self, argv=None):
         self.options = self.parser.parse_args(argv)

@@ -36,8 +36,9 @@ extern "C" {
  * 7 = round 6: bbd_bn_act_grouped_dev_fwd / _bwd (group table resident on the device: launches whose arguments do not
  * depend on the batch signature); 8 = bbd_disp_viz / bbd_disp_viz_scratch_ints (single-image prediction);
  * 9 = bbd_velo_depth / bbd_velo_depth_scratch_ints (ground-truth depth maps from Velodyne scans);
- * 10 = bbd_syns_* / bbd_chamfer_nn (SYNS-Patches evaluation: edge and point-cloud metrics). */
-#define BBD_ABI_VERSION 10
+ * 10 = bbd_syns_* / bbd_chamfer_nn (SYNS-Patches evaluation: edge and point-cloud metrics);
+ * 11 = bbd_pose_ate (KITTI odometry evaluation: chained poses, local ground truth, trajectory error). */
+#define BBD_ABI_VERSION 11
 
 /* Source frames live in separate tensors, one per frame id (inputs[("color", f, 0)],
  * trainer.py:428).  A "slot" indexes a host array of their base pointers. */
@@ -396,6 +397,20 @@ int bbd_syns_pointcloud(const float* pred, const float* gt, const int32_t* desc,
                         const float* inv_K, int32_t* scratch, int scratch_ints, float* out, int n, int h, int w,
                         int px_stride, int max_h, int max_w, double min_depth, double max_depth, double clamp_lo,
                         double clamp_hi, double th, int flags, void* stream);
+
+/* ---- KITTI odometry evaluation (evaluate_pose.py:18-41, :101-116, :125-159): everything after the pose
+ * network, for all windows of a sequence in one call - three small launches, no host synchronisation, no atomics
+ * (identical calls give identical bytes).  Arithmetic and its order: csrc/bbd_odom_math.h.
+ *   poses    float32 [1+S, N, 16]: section 0 = the direct pose of window i (frames i, i+S); section 1+k = the single-step
+ *            pose of frames (i+k, i+k+1), k = 0..S-1
+ *   gt       float64 [M, 12]: the rows of the KITTI poses file (3x4, row-major); (0 0 0 1) is appended here
+ *   chained  float32 [N, 16] out: step_{S-1} @ ... @ step_0, rounded like torch.matmul on the CPU
+ *   gt_local float64 [M-S, 16] out: inv(inv(G[j]) . G[j+S]) with a general (Gauss-Jordan, partial pivoting) inverse
+ *   ates     float64 [2, N-S] out: row 0 direct, row 1 chained; track i takes min(L, N-i) poses; 0/0 stays NaN
+ *   summary  float64 [2, 4] out: mean, population std, count, 0 per row; NaN when count == 0 or a track is NaN
+ * S < 1, L < 1, N < 0 or N > M - S return BBD_E_BADARG.  An output without elements may be NULL. */
+int bbd_pose_ate(const float* poses, const double* gt, float* chained, double* gt_local, double* ates, double* summary,
+                 int N, int M, int S, int L, void* stream);
 
 /* ---- Loader image pipeline: replaces the per-item Pillow/torchvision work of
  * datasets/mono_dataset.py:186-205 (Resize(LANCZOS) chain, ColorJitter, ToTensor) and the stacking of
