@@ -20,7 +20,7 @@ PROJ_STRIDE = 24
 KIND_WARP, KIND_IDENT, FLAG_NO_POSE_GRAD = 0, 1, 0x100
 COMPOSE_STRIDE, COMPOSE_ERROR, COMPOSE_REPLACE = 12, 1, 2
 PAIR_SHIFT = 16        # bits 16-23 of bbd_cand_t.kind: 1 + index of the pass partner (hint), 0 = none
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 _p = ctypes.c_void_p
 _i = ctypes.c_int
@@ -73,6 +73,7 @@ SIGNATURES = {
     "bbd_chamfer_nn": [_p, _p, _i, _i, _p, _p, _p],
     "bbd_syns_pointcloud": [_p] * 6 + [_i, _p] + [_i] * 6 + [_d] * 5 + [_i, _p],
     "bbd_pose_ate": [_p] * 6 + [_i] * 4 + [_p],
+    "bbd_post_process_disp": [_p, _p, _i, _i, _i, _p],
     "bbd_resample_h_u8": [_p, _p, _p, _i, _i, _p, _p, _i, _p],
     "bbd_resample_v_u8": [_p, _p, _p, _i, _i, _i, _p, _p, _i, _p],
     "bbd_color_jitter_u8": [_p, _p, _p, _i, _i, _i, _p, _p],

@@ -288,16 +288,39 @@ def evaluate(opt, dataloader=None, gt_depths=None, models=None, batch_size=16, g
     `opt.eval_split == "SYNS"` is the reference's SYNS-Patches branch: frames from `opt.syns_path`, `gt_depths.npz` and
     `gt_edges.npz` from the split directory (or `gt_depths` / `gt_edges`), depth range (1e-3, 125), no crop, and the
     7-column table abs_rel, err, sq_rel, rmse, rmse_log, edge_Acc, edge_comp - 9 columns with f1 and iou1 under
-    `opt.chamfer` (`syns_metrics`).  Returns (mean_errors[7 or 9], ratios)."""
+    `opt.chamfer` (`syns_metrics`).  Returns (mean_errors[7 or 9], ratios).
+
+    Four options of the Monodepth2 family, each read with a default so that an `opt` without them behaves as before
+    (DESIGN.md 6e), in both branches:
+      `post_process`      every batch goes through the networks together with its left-right flipped copy and the two
+                          predictions are blended by `ops.post_process_disp`; the blended disparities are scored.
+      `save_pred_disps`   the scored disparities stay on the device, are concatenated and copied to the host once and
+                          written to `<load_weights_folder>/disps_<eval_split>_split.npy` as float32 [N,h,w].
+      `ext_disp_to_eval`  path of such a file: its disparities are scored instead of predictions - no weights, no
+                          dataset, no loader.  `post_process` and `save_pred_disps` concern predictions and do nothing.
+      `no_eval`           stop after the predictions (and the optional save): no ground truth is loaded, nothing is
+                          scored, (None, None) is returned."""
     from . import tuning
     tuning.use_shipped_db()      # (no Trainer is built here: the tuned MIOpen database is wired explicitly)
     import os
     from . import datasets, networks
-    from .layers import disp_to_depth
 
     assert sum((opt.eval_mono, opt.eval_stereo)) == 1, \
         "Please choose mono or stereo evaluation by setting either --eval_mono or --eval_stereo"
     device = torch.device("cuda:%d" % getattr(opt, "cuda", 0))
+    ext = getattr(opt, "ext_disp_to_eval", None)
+    no_eval = bool(getattr(opt, "no_eval", False))
+    split_dir = os.path.join(getattr(opt, "splits_dir", "splits"), opt.eval_split)
+    syns = opt.eval_split == "SYNS"
+
+    def score(source, save_path):
+        if syns:
+            return _evaluate_syns(opt, source, save_path, no_eval, gt_depths, gt_edges, inv_K, split_dir, device)
+        return _evaluate_kitti(opt, source, save_path, no_eval, gt_depths, split_dir, device)
+
+    if ext is not None:
+        return score(_ExternalDisps(ext, batch_size, device), None)
+    save_path = _disps_path(opt) if getattr(opt, "save_pred_disps", False) else None      # raises before any prediction
     if models is None:
         folder = os.path.expanduser(opt.load_weights_folder)
         assert os.path.isdir(folder), "Cannot find a folder at {}".format(folder)
@@ -319,8 +342,6 @@ def evaluate(opt, dataloader=None, gt_depths=None, models=None, batch_size=16, g
         height, width = opt.height, opt.width
     encoder.to(device).eval()
     decoder.to(device).eval()
-    split_dir = os.path.join(getattr(opt, "splits_dir", "splits"), opt.eval_split)
-    syns = opt.eval_split == "SYNS"
     if dataloader is None:
         filenames = datasets.readlines(os.path.join(split_dir, "test_files.txt"))
         if syns:                                         # evaluate_depth.py:128-132
@@ -331,8 +352,87 @@ def evaluate(opt, dataloader=None, gt_depths=None, models=None, batch_size=16, g
                                           naive_mix=True)
         dataloader = datasets.DeviceLoader(ds, batch_size, datasets.DeviceCollate(height, width, [0], device),
                                            shuffle=False, drop_last=False, num_workers=getattr(opt, "num_workers", 8))
-    if syns:
-        return _evaluate_syns(opt, dataloader, gt_depths, gt_edges, inv_K, encoder, decoder, split_dir, device)
+    return score(_PredictedDisps(opt, dataloader, encoder, decoder, bool(getattr(opt, "post_process", False))), save_path)
+
+
+class _PredictedDisps:
+    """The disparities that are scored, batch by batch on the device: `disp_to_depth` of the networks' output and, with
+    `post_process`, the flip blend of the batch and its mirrored copy ([n,h,w] then, [n,1,h,w] otherwise)."""
+    count = None                 # known only after the loader has run dry
+
+    def __init__(self, opt, dataloader, encoder, decoder, post_process):
+        self.opt, self.dataloader, self.encoder, self.decoder = opt, dataloader, encoder, decoder
+        self.post_process = post_process
+
+    def __iter__(self):
+        from .layers import disp_to_depth
+        for data in self.dataloader:
+            x = data[("color", 0, 0)]
+            if self.post_process:
+                x = torch.cat((x, torch.flip(x, [3])), 0)
+            out = self.decoder(self.encoder(x))
+            pred_disp, _ = disp_to_depth(out[("disp", 0)], self.opt.min_depth, self.opt.max_depth)
+            yield ops.post_process_disp(pred_disp) if self.post_process else pred_disp
+
+
+class _ExternalDisps:
+    """Disparities of a saved file (`--ext_disp_to_eval`): a numeric [N,h,w] array, cast to float32 and uploaded in
+    batches of `batch_size`."""
+
+    def __init__(self, path, batch_size, device):
+        arr = np.load(path)
+        if not isinstance(arr, np.ndarray) or arr.ndim != 3 or arr.dtype.kind not in "fiu" or 0 in arr.shape:
+            raise ValueError("ext_disp_to_eval: %s must hold a numeric [N,h,w] array, got %s"
+                             % (path, "%s %s" % (arr.dtype, arr.shape) if isinstance(arr, np.ndarray) else type(arr)))
+        print("-> Loading predictions from {}".format(path))
+        self.arr, self.batch_size, self.device, self.count = arr, max(1, int(batch_size)), device, arr.shape[0]
+
+    def __iter__(self):
+        for first in range(0, self.count, self.batch_size):
+            chunk = np.ascontiguousarray(self.arr[first:first + self.batch_size], dtype=np.float32)
+            yield torch.from_numpy(chunk).to(self.device)
+
+
+def _disps_path(opt):
+    """Where `save_pred_disps` writes (Monodepth2: disps_<split>_split.npy in the weights folder)."""
+    import os
+    folder = getattr(opt, "load_weights_folder", None)
+    if folder is None or str(folder) == "None":
+        raise ValueError("save_pred_disps writes into load_weights_folder, which is not set")
+    return os.path.join(os.path.expanduser(str(folder)), "disps_{}_split.npy".format(opt.eval_split))
+
+
+def _save_disps(kept, save_path):
+    """All scored disparities as ONE float32 [N,h,w] array: concatenated on the device, one copy to the host."""
+    disps = torch.cat([d[:, 0] if d.dim() == 4 else d for d in kept]).float().cpu().numpy()
+    print("-> Saving predicted disparities to ", save_path)
+    np.save(save_path, disps)
+
+
+def _predict_only(source, save_path):
+    """`no_eval`: the predictions and the optional save, nothing else (a saved file is only checked, not uploaded)."""
+    kept = []
+    with torch.no_grad():
+        for pred_disp in (() if isinstance(source, _ExternalDisps) else source):
+            if save_path is not None:
+                kept.append(pred_disp)
+    if save_path is not None:
+        _save_disps(kept, save_path)
+    print("-> Evaluation disabled. Done.")
+    return None, None
+
+
+def _check_count(source, gts):
+    if source.count is not None and source.count != len(gts):
+        raise ValueError("ext_disp_to_eval holds %d disparity maps, the ground truth of the split %d"
+                         % (source.count, len(gts)))
+
+
+def _evaluate_kitti(opt, source, save_path, no_eval, gt_depths, split_dir, device):
+    """The KITTI splits: every batch of `source` is scored by one `bbd_depth_metrics` launch while it is in HBM."""
+    import os
+    if no_eval:
+        return _predict_only(source, save_path)
     gt_path = os.path.join(split_dir, "gt_depths.npz")
     if gt_depths is None and not os.path.isfile(gt_path) and opt.eval_split in ("eigen", "eigen_zhou"):
         # what export_gt_depth.py would have written, straight into the device buffer the metrics read
@@ -344,22 +444,25 @@ def evaluate(opt, dataloader=None, gt_depths=None, models=None, batch_size=16, g
     if gt_depths is None:
         gt_depths = np.load(gt_path, fix_imports=True, encoding="latin1", allow_pickle=True)["data"]
     gts = gt_depths if isinstance(gt_depths, GroundTruthSet) else GroundTruthSet(gt_depths, device)
+    _check_count(source, gts)
 
     median_scaling = not opt.disable_median_scaling
     scale = opt.pred_depth_scale_factor
     if opt.eval_stereo:                                   # evaluate_depth.py:233-237
         median_scaling, scale = False, STEREO_SCALE_FACTOR
-    rows, first = [], 0
+    rows, kept, first = [], [], 0
     with torch.no_grad():
-        for data in dataloader:
-            out = decoder(encoder(data[("color", 0, 0)]))
-            pred_disp, _ = disp_to_depth(out[("disp", 0)], opt.min_depth, opt.max_depth)
+        for pred_disp in source:
             n = pred_disp.shape[0]
+            if save_path is not None:
+                kept.append(pred_disp)
             rows.append(depth_metrics(pred_disp, gts, list(range(first, first + n)), min_depth=1e-3, max_depth=80.0,
                                       pred_is_disp=True, median="numpy", median_scaling=median_scaling,
                                       scale_factor=scale))
             first += n
-    rows = torch.cat(rows).cpu().numpy().astype(np.float64)          # the only host synchronisation
+    if save_path is not None:
+        _save_disps(kept, save_path)
+    rows = torch.cat(rows).cpu().numpy().astype(np.float64)          # the only host synchronisation of the scoring
     assert first == len(gts), "split has %d images, ground truth %d" % (first, len(gts))
     mean_errors = rows[:, :7].mean(0)
     ratios = rows[:, 7] if median_scaling else None
@@ -371,12 +474,13 @@ def evaluate(opt, dataloader=None, gt_depths=None, models=None, batch_size=16, g
     return mean_errors, ratios
 
 
-def _evaluate_syns(opt, dataloader, gt_depths, gt_edges, inv_K, encoder, decoder, split_dir, device):
+def _evaluate_syns(opt, source, save_path, no_eval, gt_depths, gt_edges, inv_K, split_dir, device):
     """evaluate_depth.py with `--eval_split SYNS [--chamfer]`: every batch is scored while it is in HBM; the rows are
     read back once, at the end."""
     import os
     from . import datasets
-    from .layers import disp_to_depth
+    if no_eval:
+        return _predict_only(source, save_path)
     if gt_depths is None:
         gt_depths = np.load(os.path.join(split_dir, "gt_depths.npz"), fix_imports=True, encoding="latin1",
                             allow_pickle=True)["data"]
@@ -385,6 +489,7 @@ def _evaluate_syns(opt, dataloader, gt_depths, gt_edges, inv_K, encoder, decoder
                            allow_pickle=True)["data"]
     gts = gt_depths if isinstance(gt_depths, GroundTruthSet) else GroundTruthSet(gt_depths, device, crop=False,
                                                                                  edges=gt_edges)
+    _check_count(source, gts)
     chamfer = bool(getattr(opt, "chamfer", False))
     if chamfer and inv_K is None:
         inv_K = datasets.SYNSRAWDataset.load_intrinsic_syns()[1]
@@ -392,18 +497,21 @@ def _evaluate_syns(opt, dataloader, gt_depths, gt_edges, inv_K, encoder, decoder
     scale = opt.pred_depth_scale_factor
     if opt.eval_stereo:
         median_scaling, scale = False, STEREO_SCALE_FACTOR
-    out, ratio_rows, first = [], [], 0
+    out, ratio_rows, kept, first = [], [], [], 0
     with torch.no_grad():
-        for data in dataloader:
-            pred_disp, _ = disp_to_depth(decoder(encoder(data[("color", 0, 0)]))[("disp", 0)], opt.min_depth, opt.max_depth)
+        for pred_disp in source:
             n = pred_disp.shape[0]
+            if save_path is not None:
+                kept.append(pred_disp)
             res, rows = syns_metrics(pred_disp, gts, list(range(first, first + n)), inv_K=inv_K, chamfer=chamfer,
                                      mode="evaluate", median_scaling=median_scaling, scale_factor=scale,
                                      return_rows=True)
             out.append(res)
             ratio_rows.append(rows[:, 7])
             first += n
-    out = torch.cat(out).cpu().numpy()                                  # the only host synchronisation
+    if save_path is not None:
+        _save_disps(kept, save_path)
+    out = torch.cat(out).cpu().numpy()                                  # the only host synchronisation of the scoring
     ratios = torch.cat(ratio_rows).cpu().numpy().astype(np.float64) if median_scaling else None
     assert first == len(gts), "split has %d images, ground truth %d" % (first, len(gts))
     ncol = 9 if chamfer else 7

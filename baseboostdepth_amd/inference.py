@@ -104,14 +104,22 @@ class DepthPredictor:
             cudnn.deterministic = was
         return outs[0] if len(outs) == 1 else torch.cat(outs)
 
-    def predict(self, images, want_float=False):
+    def predict(self, images, want_float=False, post_process=False):
+        """`post_process`: the prepared batch goes through the networks together with its left-right flipped copy and
+        the two raw disparities of every image are blended (`ops.post_process_disp`, Monodepth2's flip
+        post-processing) before they are coloured; `last_disp` then holds the blend, [n,h,w]."""
         if not len(images):
             return []
         sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
         with torch.no_grad():
             self.encoder.eval()
             self.decoder.eval()
-            disp = self.last_disp = self.disparity(self.prepare(images))      # kept for inspection (tests)
+            x = self.prepare(images)
+            if post_process:
+                disp = ops.post_process_disp(self.disparity(torch.cat((x, torch.flip(x, [3])), 0)), self.backend)
+            else:
+                disp = self.disparity(x)
+            self.last_disp = disp                                              # kept for inspection (tests)
             colour, floats, stats = ops.disp_viz(disp, sizes, self.min_depth, self.max_depth, 95.0, want_float,
                                                  self.backend)
             buffers = [ops.viz_buffer(colour), stats] + ([ops.viz_buffer(floats)] if want_float else [])
@@ -151,6 +159,8 @@ def parse_args(argv=None):
     parser.add_argument("--save_npy", action="store_true",
                         help="also write <name>_disp.npy: the scaled disparity, float32, at the original size")
     parser.add_argument("--batch_size", type=int, default=16, help="images per device batch")
+    parser.add_argument("--post_process", action="store_true",
+                        help="blend the prediction with that of the flipped image (Monodepth2's post-processing)")
     parser.epilog = ("Inputs whose names end in _disp.jpg or _Base.jpg are skipped, so that a second run over a "
                      "folder of jpg files does not colour its own outputs.")
     return parser.parse_args(argv)
@@ -204,7 +214,10 @@ def run_cli(args, predictor=None):
             images = list(loads[k])
             if k + 1 < len(chunks):
                 loads.append(pool.map(_load, chunks[k + 1]))
-            results = predictor.predict(images, want_float=args.save_npy)
+            if getattr(args, "post_process", False):        # an injected predictor meets the keyword only when it is set
+                results = predictor.predict(images, want_float=args.save_npy, post_process=True)
+            else:
+                results = predictor.predict(images, want_float=args.save_npy)
             pending += [pool.submit(_save, out_dir, p, r, args.save_npy) for p, r in zip(chunk, results)]
         written = [f.result() for f in pending]
     print("-> Done!")

@@ -1626,3 +1626,27 @@ def chamfer_nn(a, b, backend=None):
     nn_b = torch.empty(b.shape[0], dtype=torch.float32, device=a.device)
     backend.run("bbd_chamfer_nn", a, ptr(a), ptr(b), a.shape[0], b.shape[0], ptr(nn_a), ptr(nn_b))
     return nn_a, nn_b
+
+
+# ---------------------------------------------------------------------------- flip post-processing
+def post_process_disp(disp, backend=None):
+    """Monodepth2's `batch_post_process_disparity(l, r[:, :, ::-1])` in ONE `bbd_post_process_disp` launch: `disp`
+    [2n,1,h,w] or [2n,h,w] float32 holds the predictions for n images followed by the predictions for the same images
+    flipped left-right (`torch.cat((x, torch.flip(x, [3])), 0)` through the networks), the second half still flipped.
+    Returns the blended disparities, float32 [n,h,w]: the reference's float64 blend rounded once."""
+    backend = backend or default_backend()
+    disp = disp.detach()
+    if disp.dim() == 4:
+        assert disp.shape[1] == 1
+        disp = disp[:, 0]
+    if disp.dim() != 3:
+        raise ValueError("post_process_disp: disp must be [2n,1,h,w] or [2n,h,w], got %s" % (tuple(disp.shape),))
+    if disp.shape[0] < 2 or disp.shape[0] % 2:
+        raise ValueError("post_process_disp: the leading dimension holds n predictions and their n flipped twins; "
+                         "%d is not a positive even number" % disp.shape[0])
+    disp = disp.contiguous().float()
+    backend._check(disp)
+    n, h, w = disp.shape[0] // 2, disp.shape[1], disp.shape[2]
+    out = torch.empty(n, h, w, dtype=torch.float32, device=disp.device)
+    backend.run("bbd_post_process_disp", disp, ptr(disp), ptr(out), n, h, w)
+    return out

@@ -41,6 +41,8 @@ _FLAGS = [
     ("--disable_median_scaling", dict(action="store_true")), ("--pred_depth_scale_factor", dict(type=float, default=1)),
     ("--eval_split", dict(type=str, default="eigen")), ("--save_pred_disps", dict(action="store_true")),
     ("--post_process", dict(action="store_true")),
+    # score a saved disps_<split>_split.npy instead of predictions / stop after predicting (and saving)
+    ("--ext_disp_to_eval", dict(type=str, default=None)), ("--no_eval", dict(action="store_true")),
     # this build
     # MonoViT (BASELINE configs[4]): MPViT-small encoder + HR decoder, AdamW with two LR groups
     ("--ViT", dict(action="store_true")), ("--mpvit_checkpoint", dict(type=str, default="./ckpt/mpvit_small.pth")),

@@ -37,8 +37,9 @@ extern "C" {
  * depend on the batch signature); 8 = bbd_disp_viz / bbd_disp_viz_scratch_ints (single-image prediction);
  * 9 = bbd_velo_depth / bbd_velo_depth_scratch_ints (ground-truth depth maps from Velodyne scans);
  * 10 = bbd_syns_* / bbd_chamfer_nn (SYNS-Patches evaluation: edge and point-cloud metrics);
- * 11 = bbd_pose_ate (KITTI odometry evaluation: chained poses, local ground truth, trajectory error). */
-#define BBD_ABI_VERSION 11
+ * 11 = bbd_pose_ate (KITTI odometry evaluation: chained poses, local ground truth, trajectory error);
+ * 12 = bbd_post_process_disp (depth evaluation: flip post-processing of the predicted disparities). */
+#define BBD_ABI_VERSION 12
 
 /* Source frames live in separate tensors, one per frame id (inputs[("color", f, 0)],
  * trainer.py:428).  A "slot" indexes a host array of their base pointers. */
@@ -397,6 +398,19 @@ int bbd_syns_pointcloud(const float* pred, const float* gt, const int32_t* desc,
                         const float* inv_K, int32_t* scratch, int scratch_ints, float* out, int n, int h, int w,
                         int px_stride, int max_h, int max_w, double min_depth, double max_depth, double clamp_lo,
                         double clamp_hi, double th, int flags, void* stream);
+
+/* Flip post-processing of predicted disparities (Monodepth2's batch_post_process_disparity; evaluate_depth.py
+ * --post_process), n images per call.
+ *   disp  float32 [2n,h,w]: rows 0..n-1 are the predictions for n images, rows n..2n-1 the predictions for the same
+ *         images flipped left-right, STILL flipped (they are read mirrored, never flipped back in memory)
+ *   out   float32 [n,h,w]; must not overlap disp
+ * With ld = disp[i][y][x], rd = disp[n+i][y][w-1-x], m = (ld + rd) * 0.5f in float32, l = np.linspace(0, 1, w) and
+ * lm(x) = 1 - clip(20 * (l[x] - 0.05), 0, 1), a = lm(x), b = lm(w-1-x) in float64:
+ *   out[i][y][x] = (float)((b * ld + a * rd) + ((1 - a) - b) * m)
+ * - the float64 blend of the reference rounded once to float32 (operation order: csrc/bbd_postproc_math.h).  One
+ * launch, no LDS, no atomics, no host synchronisation; identical calls give identical bytes.  A NULL pointer or n, h
+ * or w below 1 returns BBD_E_BADARG and launches nothing. */
+int bbd_post_process_disp(const float* disp, float* out, int n, int h, int w, void* stream);
 
 /* ---- KITTI odometry evaluation (evaluate_pose.py:18-41, :101-116, :125-159): everything after the pose
  * network, for all windows of a sequence in one call - three small launches, no host synchronisation, no atomics
