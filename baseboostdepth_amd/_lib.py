@@ -74,6 +74,9 @@ SIGNATURES = {
     "bbd_syns_pointcloud": [_p] * 6 + [_i, _p] + [_i] * 6 + [_d] * 5 + [_i, _p],
     "bbd_pose_ate": [_p] * 6 + [_i] * 4 + [_p],
     "bbd_post_process_disp": [_p, _p, _i, _i, _i, _p],
+    "bbd_train_panel_scratch_ints": [_i],
+    "bbd_train_panel": [_p] * 6 + [_i] * 6 + [_p],
+    "bbd_argmin_hist": [_p, _p, _i, _i, _p],
     "bbd_resample_h_u8": [_p, _p, _p, _i, _i, _p, _p, _i, _p],
     "bbd_resample_v_u8": [_p, _p, _p, _i, _i, _i, _p, _p, _i, _p],
     "bbd_color_jitter_u8": [_p, _p, _p, _i, _i, _i, _p, _p],
@@ -122,6 +125,7 @@ SIGNATURES = {
 RESAMPLE_JOB, RESAMPLE_FLIP, JITTER_JOB, CONVERT_JOB = 12, 1, 12, 4
 EVAL_DESC, EVAL_OUT = 8, 12
 VIZ_DESC = 4
+PANEL_DESC, PANEL_COLOR, PANEL_WARP, PANEL_SCALAR, PANEL_ARGMIN, PANEL_LUT_ROWS = 8, 0, 1, 2, 3, 532
 VELO_DESC, VELO_VEL_DEPTH = 8, 1
 SYNS_OUT, SYNS_CLOUD_OUT, SYNS_RAYS_PIXEL = 8, 8, 8
 EVAL_PRED_IS_DISP, EVAL_MEDIAN_MIDPOINT, EVAL_NO_MEDIAN_SCALING = 1, 2, 4
@@ -193,6 +197,9 @@ class HipLibrary:
 
     def disp_viz_scratch_ints(self, n):
         return self._dll.bbd_disp_viz_scratch_ints(n)
+
+    def train_panel_scratch_ints(self, n_tiles):
+        return self._dll.bbd_train_panel_scratch_ints(n_tiles)
 
     def velo_depth_scratch_ints(self, total_pixels, n_frames):
         return self._dll.bbd_velo_depth_scratch_ints(total_pixels, n_frames)

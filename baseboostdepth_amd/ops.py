@@ -1650,3 +1650,103 @@ def post_process_disp(disp, backend=None):
     out = torch.empty(n, h, w, dtype=torch.float32, device=disp.device)
     backend.run("bbd_post_process_disp", disp, ptr(disp), ptr(out), n, h, w)
     return out
+
+
+# ---------------------------------------------------------------------------- training-log panel
+_PANEL_LUTS = {}
+
+
+def panel_luts(device="cpu"):
+    """uint8 [256 + 256 + 20, 3]: plasma, magma, the categorical palette (`tab20`) - the LUT buffer of `train_panel`.
+    Read from the shipped tables (panel_luts.hex, written by tools/make_panel_luts.py, and magma_lut.hex); matplotlib is
+    never imported."""
+    key = str(device)
+    if key not in _PANEL_LUTS:
+        if "cpu" not in _PANEL_LUTS:
+            with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "panel_luts.hex")) as f:
+                rows = [line.strip() for line in f if line.strip()]
+            assert len(rows) == 276 and all(len(r) == 6 for r in rows)
+            own = torch.tensor([[int(r[0:2], 16), int(r[2:4], 16), int(r[4:6], 16)] for r in rows], dtype=torch.uint8)
+            _PANEL_LUTS["cpu"] = torch.cat([own[:256], magma_lut("cpu"), own[256:]], 0).contiguous()
+            assert _PANEL_LUTS["cpu"].shape[0] == _lib.PANEL_LUT_ROWS
+        _PANEL_LUTS[key] = _PANEL_LUTS["cpu"].to(device)
+    return _PANEL_LUTS[key]
+
+
+def _addr_words(t):
+    a = 0 if t is None else t.data_ptr()
+    lo, hi = a & 0xFFFFFFFF, (a >> 32) & 0xFFFFFFFF
+    return lo - (1 << 32) if lo >= 1 << 31 else lo, hi - (1 << 32) if hi >= 1 << 31 else hi
+
+
+def train_panel(tiles, pose_table, H, W, rows, cols, backend=None):
+    """A grid of `rows` x `cols` tiles of H x W pixels rendered on the device in ONE `bbd_train_panel` call (two
+    launches, no host synchronisation) -> (panel uint8 [rows*H, cols*W, 3], stats fp32 [len(tiles), 2]).
+
+    `tiles` is a list of `(row, col, kind, ...)`:
+        (r, c, "color", image [3,H,W])                      fp32 in [0,1], rounded to nearest
+        (r, c, "warp", source [3,H,W], depth [H,W], p)      the fused forward's warp with row p of `pose_table`
+        (r, c, "scalar", plane [H,W], "plasma" | "magma")   colour-mapped between its minimum and maximum; stats[t]
+        (r, c, "argmin", ids uint8 [H,W], n_T, n_E)         palette[id] | palette[id - n_T] >> 1 | black
+    Cells no tile names are black.  `pose_table` is [NP,40] in the row layout of `pose_table_rows` (None where no tile
+    warps)."""
+    backend = backend or default_backend()
+    if not tiles:
+        raise ValueError("train_panel: no tiles")
+    dev = tiles[0][3].device
+    if pose_table is None:
+        pose_table = torch.zeros(1, POSE_STRIDE, dtype=torch.float32, device=dev)
+    pose_table = pose_table.detach()
+    assert pose_table.dim() == 2 and pose_table.shape[1] == POSE_STRIDE and pose_table.dtype == torch.float32
+    pose_table = pose_table.contiguous()
+    kinds = {"color": _lib.PANEL_COLOR, "warp": _lib.PANEL_WARP, "scalar": _lib.PANEL_SCALAR, "argmin": _lib.PANEL_ARGMIN}
+    desc, keep = [], [pose_table]
+    for tile in tiles:
+        r, c, kind = int(tile[0]), int(tile[1]), tile[2]
+        if not (0 <= r < rows and 0 <= c < cols):
+            raise ValueError("train_panel: cell (%d, %d) outside the %d x %d grid" % (r, c, rows, cols))
+        src, aux, p0, p1 = tile[3].detach(), None, 0, 0
+        if kind in ("color", "warp"):
+            assert src.dtype == torch.float32 and tuple(src.shape) == (3, H, W), (kind, tuple(src.shape))
+        if kind == "warp":
+            aux, p0 = tile[4].detach(), int(tile[5])
+            assert aux.dtype == torch.float32 and tuple(aux.shape) == (H, W)
+            aux = aux.contiguous()
+        elif kind == "scalar":
+            assert src.dtype == torch.float32 and tuple(src.shape) == (H, W)
+            p0 = {"plasma": 0, "magma": 1}[tile[4]]
+        elif kind == "argmin":
+            assert src.dtype == torch.uint8 and tuple(src.shape) == (H, W)
+            p0, p1 = int(tile[4]), int(tile[5])
+        elif kind != "color":
+            raise ValueError("train_panel: unknown tile kind %r" % (kind,))
+        src = src.contiguous()
+        backend._check(src, aux)
+        keep += [src, aux]
+        desc.append((kinds[kind], r * cols + c) + _addr_words(src) + _addr_words(aux) + (p0, p1))
+    backend._check(pose_table)
+    n = len(desc)
+    desc = torch.tensor(desc, dtype=torch.int32)
+    if dev.type == "cuda":
+        desc = desc.pin_memory().to(dev, non_blocking=True)
+    out = torch.empty(rows * H, cols * W, 3, dtype=torch.uint8, device=dev)
+    stats = torch.zeros(n, 2, dtype=torch.float32, device=dev)
+    scratch = torch.empty(backend.lib.train_panel_scratch_ints(n), dtype=torch.int32, device=dev)
+    backend.run("bbd_train_panel", out, ptr(desc), ptr(pose_table), ptr(panel_luts(dev)), ptr(out), ptr(stats), ptr(scratch),
+                n, pose_table.shape[0], int(H), int(W), int(rows), int(cols))
+    del keep                      # (held until here: a temporary's memory is reused at once, in stream order after the launch)
+    return out, stats
+
+
+def argmin_hist(argmin, backend=None):
+    """int32 [B, MAX_CAND]: how many pixels of each sample every arg-min id won (`argmin` uint8 [B,H,W]); ids of
+    MAX_CAND and above are not counted.  One `bbd_argmin_hist` call: integer atomics, exact."""
+    backend = backend or default_backend()
+    argmin = argmin.detach()
+    assert argmin.dtype == torch.uint8 and argmin.dim() == 3
+    argmin = argmin.contiguous()
+    backend._check(argmin)
+    B, n_px = argmin.shape[0], argmin.shape[1] * argmin.shape[2]
+    counts = torch.empty(B, _lib.MAX_CAND, dtype=torch.int32, device=argmin.device)
+    backend.run("bbd_argmin_hist", argmin, ptr(argmin), ptr(counts), B, n_px)
+    return counts

@@ -58,6 +58,10 @@ _FLAGS = [
     # early curriculum: 0 = pad the pose pass to the next measured row count (32 | 48 for batch 12); "max" or a number = ONE
     # row count for the whole phase (one graph; the pass then always runs the phase's largest size)
     ("--early_pose_rows", dict(type=str, default="0")),
+    # the training log at every --log_frequency-th step (trainlog.py): off | text = progress lines on stdout + scalars.jsonl |
+    # panels = text + pictures rendered on the device (target, disparity, minimum-loss map, arg-min map, the warps)
+    ("--train_log", dict(type=str, default="off", choices=["off", "text", "panels"])),
+    ("--log_samples", dict(type=int, default=1)),
 ]
 # other zoos / datasets of the reference: parsed, refused when set
 _OUT_OF_SCOPE = ["--SYNS_eval", "--SQL", "--SQL_L", "--CA_depth", "--DIFFNet", "--stereo_guide",

@@ -129,6 +129,14 @@ class Trainer:
         self.grad_sync = None      # set by distributed.attach(): called between backward and optimizer.step
         self.flat_grads = None
         self.epoch, self.step = 0, 0
+        level = getattr(opt, "train_log", "off")
+        if level not in ("off", "text", "panels"):
+            raise ValueError("--train_log must be off, text or panels, got %r" % (level,))
+        if level == "panels" and backend is None:
+            from . import _lib
+            if self.device.type != "cuda" or not os.path.isfile(_lib.LIB_PATH):
+                raise ValueError("--train_log panels renders its pictures with the HIP library on the GPU (there is no "
+                                 "CPU path): use --train_log text on this device")
 
     def gradient_free_parameters(self):
         """Trainable parameters no loss ever reaches: torchvision-layout ResNets carry an `fc` head the
@@ -559,13 +567,21 @@ class Trainer:
                 self.last_prewarm = self.prewarm(self.epoch)      # (graphs already captured for this phase / lr are skipped)
         last = None
         log_frequency = getattr(self.opt, "log_frequency", 0)
+        logging = getattr(self.opt, "train_log", "off") != "off" and self._rank_world()[0] == 0
+        if logging and getattr(self, "start_time", None) is None:
+            self.start_time = time.time()
         for self.batch_idx, inputs in enumerate(loader):
+            before_op_time = time.time() if logging else 0.0
             last = self.train_step(inputs)
             # the reference validates every `log_frequency` steps (trainer.py:266-283)
             if log_frequency and self.batch_idx > 0 and self.batch_idx % log_frequency == 0:
+                if logging:
+                    self._log_train_step(inputs, last, time.time() - before_op_time)
                 val_loader = self.kitti_val_loader()
                 if val_loader is not None:
                     self.last_val = self.val(val_loader)
+                    if logging:
+                        self._log_val(self.last_val)
         return last
 
     def kitti_loader(self, epoch):
@@ -1137,6 +1153,8 @@ class Trainer:
                 n = outputs["depth", 0, 0].shape[0]
                 self.compute_depth_losses(outputs, losses, list(range(images, images + n)), accumulate=True)
                 images += n
+                if getattr(self.opt, "train_log", "off") == "panels":
+                    self._last_val_batch = (inputs, outputs)           # what `log("val", ...)` draws
         result = {name: float(losses[name]) / max(images, 1) for name in self.depth_metric_names}
         if result["de/abs_rel"] < getattr(self, "best", float("inf")):
             self.best = result["de/abs_rel"]
@@ -1173,6 +1191,126 @@ class Trainer:
             if self.plan.decomp and m != 0:
                 dictor_guide[(key(m), "guide")].append(guide[rows])
         return dictor_norm, dictor_guide
+
+    # ------------------------------------------------------------------ training log (trainer.py:259-284, :667-772)
+    def _trainlog(self):
+        if getattr(self, "trainlog", None) is None:
+            from .trainlog import TrainLog
+            self.trainlog = TrainLog(self.log_path, self.opt.batch_size)
+        return self.trainlog
+
+    def _log_train_step(self, inputs, step_result, duration):
+        """The reference's block at trainer.py:266-282 for the step that has just run: the `log_time` line, the context
+        lines, then the scalar record and (under `panels`) the picture.  `log` runs first - the loss reaches the host with
+        its one synchronisation - and the lines are printed from what it returns."""
+        outputs, losses = step_result
+        tl = self._trainlog()
+        row = self.log("train", inputs, outputs, losses)
+        total = getattr(self, "num_total_steps", 0) or (
+            len(getattr(self, "train_filenames", [])) // self.opt.batch_size * getattr(self.opt, "num_epochs", 1))
+        total = max(int(total), self.step)               # (unknown length: no estimate, "time left" reads zero)
+        tl.rule()
+        tl.log_time(self.epoch, self.batch_idx, self.step, total, duration, row["loss"], self.start_time)
+        tl.context(self.epoch, row["lr"], inputs["ordering"], self.opt.scales, self.valid_frames, inputs.get("cutt"),
+                   inputs.get("to_use"))
+        tl.rule()
+
+    def _log_val(self, result):
+        """After the validation pass of a logged step: its record, its picture, and `weights_best` when abs_rel improved
+        (the reference names a checkpoint after every validation's abs_rel, trainer.py:640-644; `resume_epoch` reads
+        `weights_best`)."""
+        self.log("val", None, None, result)
+        if result["de/abs_rel"] < getattr(self, "best_logged", float("inf")):
+            self.best_logged = result["de/abs_rel"]
+            self.save_model("best")
+
+    def log(self, mode, inputs, outputs, losses):
+        """The reference's `log(mode, inputs, outputs, losses)` without wandb (`trainlog.TrainLog`): one JSON record of the
+        scalars and, under `--train_log panels`, one PNG rendered on the device by `ops.train_panel`.
+
+        "train": every loss, the learning rate and the share of the batch's pixels (scale index 0) won by a true-pose
+        warp, an error-induced warp and an identity map; the panel shows the first `opt.log_samples` samples - per sample
+        a header row (target | plasma disparity | magma minimum-loss map | arg-min map), then one row per true-pose
+        candidate (source frame | its warp | its error-induced warp, if any | empty).
+        "val": the seven depth metrics; the panel shows the first image of the last validation batch and its disparity.
+
+        Everything the record and the picture need travels to the host together, behind ONE synchronisation; nothing
+        here runs inside a captured graph or adds to one.  Returns the record (None when logging is off or on ranks > 0)."""
+        level = getattr(self.opt, "train_log", "off")
+        if level == "off" or self._rank_world()[0] != 0:
+            return None
+        tl = self._trainlog()
+        names = [k for k in losses if k != "reprojection_losses"]
+        on_device = [k for k in names if torch.is_tensor(losses[k]) and losses[k].is_cuda]
+        fetch, counts, image = [], None, None
+        with torch.no_grad():
+            if on_device:
+                fetch.append(torch.stack([losses[k].detach().float().reshape(()) for k in on_device]))
+            if mode == "train":
+                counts = ops.argmin_hist(outputs[("bbd", "argmin")][0], self._backend())
+                fetch.append(counts)
+            if level == "panels":
+                image = self.render_panel(mode, inputs, outputs)
+                if image is not None:
+                    fetch.append(image)
+        host = tl.to_host(fetch)
+        record = {"step": self.step, "epoch": self.epoch, "batch": getattr(self, "batch_idx", 0)}
+        if on_device:
+            vals = host.pop(0)
+        for k in names:
+            v = losses[k]
+            record[k] = float(vals[on_device.index(k)]) if k in on_device else float(v.detach() if torch.is_tensor(v) else v)
+        record["lr"] = self.model_optimizer.param_groups[0]["lr"] if getattr(self, "model_optimizer", None) else 0.0
+        if mode == "train":
+            from .trainlog import argmin_fractions
+            record.update(argmin_fractions(host.pop(0).tolist(), self.plan.cand_names))
+        row = tl.scalars(mode, record)
+        if image is not None:
+            tl.panel(mode, self.step, host.pop(0))
+        return row
+
+    def panel_tiles(self, inputs, outputs):
+        """(tiles, pose table, rows, cols) of the "train" panel, for `ops.train_panel`.  The pose rows are rebuilt here,
+        outside any graph, from the step's (detached) `cam_T_cam*` outputs - in pooled form the views `with_pose_views`
+        lays over the step's pose buffers."""
+        opt, plan, be = self.opt, self.plan, self._backend()
+        H, W = opt.height, opt.width
+        depth = outputs.get(("depth", 0, 0))
+        if depth is None:
+            depth = ops.disp_to_depth_fullres(outputs[("disp", 0)].detach(), H, W, opt.min_depth, opt.max_depth, be)
+        poses = {job: T.detach() for job, T in self._job_poses(inputs, outputs).items()}
+        proj = ops.pose_table(plan, inputs[("K", 0)], inputs[("inv_K", 0)], poses)
+        disp, min_loss, argmin = outputs[("disp", 0)], outputs[("bbd", "to_optimise")][0], outputs[("bbd", "argmin")][0]
+        tiles, r = [], 0
+        for b in range(min(max(int(getattr(opt, "log_samples", 1)), 1), plan.B)):
+            names = plan.cand_names[b]
+            n_t = sum(1 for k, _ in names if k == "T")
+            n_e = sum(1 for k, _ in names if k == "E")
+            tiles += [(r, 0, "color", inputs[("color", 0, 0)][b]), (r, 1, "scalar", disp[b, 0], "plasma"),
+                      (r, 2, "scalar", min_loss[b], "magma"), (r, 3, "argmin", argmin[b], n_t, n_e)]
+            r += 1
+            for kind, f in names:
+                if kind != "T":
+                    continue
+                src = inputs[("color", f, 0)][plan.source_row(f, b)]
+                tiles += [(r, 0, "color", src), (r, 1, "warp", src, depth[b, 0], plan.pose_row("T", f, b))]
+                if ("E", f) in names:
+                    tiles.append((r, 2, "warp", src, depth[b, 0], plan.pose_row("E", f, b)))
+                r += 1
+        return tiles, proj, r, 4
+
+    def render_panel(self, mode, inputs, outputs):
+        """uint8 [rows*H, cols*W, 3] on the device (see `log`); None when there is nothing to draw."""
+        H, W, be = self.opt.height, self.opt.width, self._backend()
+        if mode == "train":
+            tiles, proj, rows, cols = self.panel_tiles(inputs, outputs)
+            return ops.train_panel(tiles, proj, H, W, rows, cols, be)[0]
+        last = getattr(self, "_last_val_batch", None) if inputs is None else (inputs, outputs)
+        if last is None:
+            return None
+        inputs, outputs = last
+        tiles = [(0, 0, "color", inputs[("color", 0, 0)][0]), (0, 1, "scalar", outputs[("disp", 0)][0, 0], "plasma")]
+        return ops.train_panel(tiles, None, H, W, 1, 2, be)[0]
 
     # ------------------------------------------------------------------ checkpoints (trainer.py:774-829)
     def save_opts(self):

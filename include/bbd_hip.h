@@ -317,6 +317,44 @@ int bbd_disp_viz(const float* disp, const int32_t* desc, const uint8_t* lut, uin
                  float* stats, int32_t* scratch, int n, int h, int w, double min_disp, double max_disp,
                  double percentile, void* stream);
 
+/* Training-log panel (csrc/bbd_panel.hip): a grid of rows x cols tiles of H x W pixels each, rendered on the device
+ * from what a training step leaves behind, into ONE uint8 RGB image out [rows*H, cols*W, 3].
+ *   desc[t] = {kind, cell = row * cols + col, src lo, src hi, aux lo, aux hi, p0, p1}      device int32 [n_tiles, 8]
+ *     (addresses as two 32-bit words, low word first)
+ *   BBD_PANEL_COLOR   src = fp32 [3,H,W] in [0,1]:  u8 = (int)(min(max(x,0),1) * 255.0f + 0.5f)  (round to nearest, so
+ *                     that a frame decoded as k / 255.0f gives its file's bytes back)
+ *   BBD_PANEL_WARP    src = source image fp32 [3,H,W], aux = depth fp32 [H,W], p0 = row of the pose table `pose`
+ *                     [NP, BBD_POSE_STRIDE] (K | T | inv_K, as bbd_pose_expand takes it): the warp of the fused forward
+ *                     - same functions of bbd_math.h in the same order, so the float that is quantised (like COLOR) is
+ *                     the bit pattern bbd_warp_ssim_min_*fwd writes to `warped`.  p0 outside [0, NP), H < 2 or W < 2:
+ *                     the tile is black.
+ *   BBD_PANEL_SCALAR  src = fp32 [H,W], p0 = 0 plasma | 1 magma:  lut[256 * p0 + bbd_viz_lut_index(v, min, max)] with
+ *                     min / max the plane's extrema without its NaNs (exact: integer maxima of order keys);
+ *                     max == min and NaN take entry 0.  stats[t] = {min, max} (NaN, NaN for a plane of NaNs).
+ *   BBD_PANEL_ARGMIN  src = uint8 [H,W] arg-min ids, p0 = n_T, p1 = n_E (true-pose / error-induced candidates of the
+ *                     sample):  id < n_T -> palette[id];  n_T <= id < n_T + n_E -> palette[id - n_T] >> 1 per channel;
+ *                     anything else (an identity candidate won: the pixel is auto-masked) -> black.
+ *   lut = uint8 [BBD_PANEL_LUT_ROWS, 3]: plasma (256), magma (256), the categorical palette (20).
+ * Every byte of `out` is written: cells no tile names are 0; of several tiles naming one cell the last wins; a tile
+ * whose cell is outside the grid or whose kind is unknown draws nothing.  stats [n_tiles, 2] is written for SCALAR
+ * tiles only.  scratch holds bbd_train_panel_scratch_ints(n_tiles) int32 and needs no initialisation.  Two launches
+ * (per-tile partial extrema; the render), no atomics, no allocation, no host synchronisation: identical calls give
+ * identical bytes.  A NULL pointer, a count or size below 1, H*W >= 2^31, rows*H or cols*W >= 2^31, rows*cols or
+ * n_tiles > 65535 return BBD_E_BADARG and launch nothing. */
+#define BBD_PANEL_DESC 8
+#define BBD_PANEL_COLOR 0
+#define BBD_PANEL_WARP 1
+#define BBD_PANEL_SCALAR 2
+#define BBD_PANEL_ARGMIN 3
+#define BBD_PANEL_LUT_ROWS 532
+int bbd_train_panel_scratch_ints(int n_tiles);
+int bbd_train_panel(const int32_t* desc, const float* pose, const uint8_t* lut, uint8_t* out, float* stats,
+                    int32_t* scratch, int n_tiles, int NP, int H, int W, int rows, int cols, void* stream);
+/* counts[b][id] = number of pixels of argmin [B, n_px] (uint8) equal to id, id < BBD_MAX_CAND; larger ids are not
+ * counted.  counts int32 [B, BBD_MAX_CAND] is zeroed on `stream` by the call; one launch, integer atomics (exact).
+ * B <= 65535. */
+int bbd_argmin_hist(const uint8_t* argmin, int32_t* counts, int B, int n_px, void* stream);
+
 /* Ground-truth depth maps from Velodyne scans (kitti_utils.py:46-98, generate_depth_map), a ragged batch of n_frames
  * frames per call, written straight into a packed float32 buffer such as evaluation.GroundTruthSet keeps.
  *   points  float32 [total points, 4]: x, y, z and a fourth column that is ignored (KITTI's reflectance, which the

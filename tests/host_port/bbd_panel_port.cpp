@@ -1,0 +1,79 @@
+// Host port of bbd_panel.hip for the CPU test tier: the same per-pixel functions (bbd_panel_math.h, bbd_math.h,
+// bbd_viz_math.h) in plain loops.  Same C signatures as bbd_train_panel / bbd_argmin_hist minus `stream`.
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+
+#include "../../include/bbd_hip.h"
+#include "../../baseboostdepth_amd/csrc/bbd_panel_math.h"
+
+namespace {
+const void* address(int32_t lo, int32_t hi) {
+  return reinterpret_cast<const void*>((uintptr_t)(uint32_t)lo | ((uintptr_t)(uint32_t)hi << 32));
+}
+}  // namespace
+
+extern "C" int hp_train_panel_scratch_ints(int n_tiles) { return n_tiles > 0 && n_tiles <= 65535 ? 2 * n_tiles : 0; }
+
+extern "C" int hp_train_panel(const int32_t* desc, const float* pose, const uint8_t* lut, uint8_t* out, float* stats,
+                              int32_t* scratch, int n_tiles, int NP, int H, int W, int rows, int cols) {
+  if (!desc || !pose || !lut || !out || !stats || !scratch) return BBD_E_BADARG;
+  if (n_tiles < 1 || NP < 1 || H < 1 || W < 1 || rows < 1 || cols < 1) return BBD_E_BADARG;
+  const long long lim = 0x7fffffffLL;
+  if ((long long)H * W > lim || (long long)rows * H > lim || (long long)cols * W > lim) return BBD_E_BADARG;
+  if ((long long)rows * cols > 65535 || n_tiles > 65535) return BBD_E_BADARG;
+  uint32_t packed[BBD_PANEL_LUT_ROWS];
+  for (int i = 0; i < BBD_PANEL_LUT_ROWS; ++i)
+    packed[i] = (uint32_t)lut[3 * i] | ((uint32_t)lut[3 * i + 1] << 8) | ((uint32_t)lut[3 * i + 2] << 16);
+  const BbdDims dm = bbd_dims(H, W);
+  const size_t hw = (size_t)H * (size_t)W, out_row = (size_t)cols * (size_t)W;
+  memset(out, 0, (size_t)rows * H * out_row * 3);
+  for (int t = 0; t < n_tiles; ++t) {                      // in table order: the last tile of a cell wins
+    const int32_t* d = desc + (size_t)t * BBD_PANEL_DESC;
+    const int kind = d[0], cell = d[1], p0 = d[6], p1 = d[7];
+    const void* src = address(d[2], d[3]);
+    const void* aux = address(d[4], d[5]);
+    if (cell < 0 || cell >= rows * cols) continue;
+    const int row = cell / cols, col = cell - row * cols;
+    const bool warp_ok = aux && p0 >= 0 && p0 < NP && H >= 2 && W >= 2;
+    float vmin = 0.0f, vmax = 0.0f, pj[21];
+    if (src && kind == BBD_PANEL_SCALAR) {
+      uint32_t inv_min = 0u, max_key = 0u;
+      for (size_t i = 0; i < hw; ++i) bbd_panel_minmax_update(static_cast<const float*>(src)[i], &inv_min, &max_key);
+      bbd_panel_minmax_values(inv_min, max_key, &vmin, &vmax);
+      stats[(size_t)t * 2] = vmin;
+      stats[(size_t)t * 2 + 1] = vmax;
+    }
+    if (src && kind == BBD_PANEL_WARP && warp_ok) bbd_make_proj(pose + (size_t)p0 * BBD_POSE_STRIDE, pj);
+    for (int y = 0; y < H; ++y)
+      for (int x = 0; x < W; ++x) {
+        const size_t i = (size_t)y * W + x;
+        uint32_t c = 0u;
+        if (!src) {
+        } else if (kind == BBD_PANEL_COLOR) {
+          c = bbd_panel_color(static_cast<const float*>(src), hw, i);
+        } else if (kind == BBD_PANEL_WARP && warp_ok) {
+          float val[3];
+          c = bbd_panel_warp(static_cast<const float*>(src), static_cast<const float*>(aux), pj, dm, x, y, val);
+        } else if (kind == BBD_PANEL_SCALAR) {
+          c = packed[(p0 == 1 ? 256 : 0) + bbd_viz_lut_index(static_cast<const float*>(src)[i], vmin, vmax)];
+        } else if (kind == BBD_PANEL_ARGMIN) {
+          c = bbd_panel_argmin_colour(packed + 512, static_cast<const uint8_t*>(src)[i], p0, p1);
+        }
+        uint8_t* o = out + (((size_t)row * H + y) * out_row + (size_t)col * W + x) * 3;
+        o[0] = (uint8_t)c; o[1] = (uint8_t)(c >> 8); o[2] = (uint8_t)(c >> 16);
+      }
+  }
+  return 0;
+}
+
+extern "C" int hp_argmin_hist(const uint8_t* argmin, int32_t* counts, int B, int n_px) {
+  if (!argmin || !counts || B < 1 || B > 65535 || n_px < 1) return BBD_E_BADARG;
+  memset(counts, 0, (size_t)B * BBD_MAX_CAND * sizeof(int32_t));
+  for (int b = 0; b < B; ++b)
+    for (int i = 0; i < n_px; ++i) {
+      const int id = argmin[(size_t)b * n_px + i];
+      if (id < BBD_MAX_CAND) counts[(size_t)b * BBD_MAX_CAND + id] += 1;
+    }
+  return 0;
+}

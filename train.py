@@ -4,6 +4,8 @@
     python train.py --kt_path /data/kitti --rand --trimin --decomp --incremental_skip --partial_skip \
                     --naive_mix --kt --weights_init scratch
     python train.py --synthetic --num_epochs 1          # no dataset: KITTI-shaped synthetic batches
+    python train.py ... --train_log panels --log_frequency 250    # progress lines, <log>/train/scalars.jsonl and
+                                                        # <log>/train/panels/step_*.png (`text`: no pictures; default off)
 
 Multi-GPU: `python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 train.py ...`
 (one process per GPU, gradients averaged over RCCL).
@@ -38,6 +40,7 @@ def main(argv=None):
         distributed.attach(trainer)
     if opts.synthetic:
         steps = int(os.environ.get("BBD_SYNTH_STEPS", "50"))
+        trainer.num_total_steps = steps * opts.num_epochs          # (the training log's "time left")
         trainer.train(lambda epoch: synthetic.synthetic_loader(
             opts.batch_size, steps, opts.height, opts.width, opts.scales, device=trainer.device,
             seed=opts.pytorch_random_seed + rank, trimin=opts.trimin, epoch=epoch))
