@@ -84,17 +84,24 @@ __global__ __launch_bounds__(NT) void token_ln_fwd_kernel(const float* __restric
       }
     }
     if (weight == nullptr) continue;
-    const float mean = row_sum<LPR>(s) * inv_c;
-    float q = 0.0f;
+    // The fp32 sum of a row far from zero loses up to ulp(sum) / C of the mean - several ulps of the mean itself, which
+    // (x - mean) * rstd then carries into every channel of z and into the weight gradient.  So the deviations are taken
+    // from that first estimate (they are small and nearly exact) and their own mean corrects it:
+    //   mean = mean0 + dm,  sum (x - mean)^2 = sum (x - mean0)^2 - C dm^2
+    const float mean0 = row_sum<LPR>(s) * inv_c;
+    float d1 = 0.0f, q = 0.0f;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
       const int c4 = sub + i * LPR;
       if (c4 < C4) {
-        const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
+        const float a = v[i].x - mean0, b = v[i].y - mean0, c = v[i].z - mean0, d = v[i].w - mean0;
+        d1 += (a + b) + (c + d);
         q += (a * a + b * b) + (c * c + d * d);
       }
     }
-    const float rstd = rsqrtf(row_sum<LPR>(q) * inv_c + eps);
+    const float dm = row_sum<LPR>(d1) * inv_c;
+    const float mean = mean0 + dm;
+    const float rstd = rsqrtf(fmaxf(row_sum<LPR>(q) * inv_c - dm * dm, 0.0f) + eps);
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
       const int c4 = sub + i * LPR;

@@ -277,6 +277,21 @@ static int wgrad_rows(long segs, int C) {
 // ------------------------------------------------------------------------------------------------------
 constexpr int FA_TOK = 16;      // tokens staged per iteration of the context kernel
 constexpr int FA_MAXO = 48;     // context entries per thread (C * Ch <= 256 * 48); instantiated for 2 / 8 / 24 / 48
+constexpr int FA_TPB = 8;       // tokens per workgroup of the two token-parallel kernels
+
+// Dynamic LDS of the four launches, in bytes: ONE function each, used by the launch site and by
+// bbd_factor_att_supported, so the predicate cannot promise a shape a launch then overruns.
+constexpr size_t FA_LDS_DEFAULT = 64 * 1024;      // what a launch may ask for without the opt-in
+constexpr size_t FA_LDS_MAX = 160 * 1024;         // what a gfx950 workgroup can have at all
+constexpr bool fa_row_form(int C, int Ch) { return Ch <= 48 && C <= 512 && C > 128; }
+constexpr size_t fa_context_lds(int C) { return (size_t)2 * FA_TOK * C * sizeof(float); }
+constexpr size_t fa_context_rows_lds(int C, int Ch) {
+  return (size_t)FA_TOK * (C + (C / Ch) * ((Ch + 3) & ~3)) * sizeof(float);
+}
+constexpr size_t fa_apply_lds(int C, int Ch) { return ((size_t)C * Ch + FA_TPB * C + C) * sizeof(float); }
+constexpr size_t fa_bwd_lds(int C, int Ch) {
+  return ((size_t)2 * C * (Ch | 1) + C + 3 * FA_TPB * C + C) * sizeof(float);
+}
 
 // per-(image, token segment) online softmax statistics of k over the tokens of the segment
 __global__ __launch_bounds__(NT) void fa_kstats_kernel(const float* __restrict__ qkv, float* __restrict__ pm,
@@ -600,16 +615,34 @@ __global__ __launch_bounds__(NT) void fa_bwd_token_kernel(const float* __restric
   }
 }
 
+// A request above the default limit needs the opt-in, once per kernel (`granted`: that kernel's high-water mark); one
+// above what a workgroup can have is refused.
+// The marks are plain statics, one per kernel and per process: hipFuncSetAttribute acts on the current device, and
+// nothing orders two host threads that raise a mark at once.  That suits what the library is used for - one process per
+// GPU, launches from one thread; a process that drives several devices, or launches from several threads, needs the
+// marks per device and atomic first.
+template <typename Kernel>
+bool fa_lds_granted(Kernel kernel, size_t lds, size_t* granted) {
+  if (lds > FA_LDS_MAX) return false;
+  if (lds <= FA_LDS_DEFAULT || lds <= *granted) return true;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+      hipSuccess)
+    return false;
+  *granted = lds;
+  return true;
+}
+
 template <bool SOFTMAX>
-void fa_launch_context(dim3 grid, size_t lds, hipStream_t st, const float* qkv, const float* bsrc, int brow,
-                              const float* kmax, const float* krsum, float* part, int N, int C, int Ch, int seg_tokens) {
+int fa_launch_context(dim3 grid, hipStream_t st, const float* qkv, const float* bsrc, int brow, const float* kmax,
+                      const float* krsum, float* part, int N, int C, int Ch, int seg_tokens) {
   // row form: heads of up to 48 channels, up to 512 rows; the padded b tile must not contain stale values that matter:
   // the pad lanes of a head only feed accumulators that are never stored
   // (narrow token rows - C <= 128, one or two waves of rows per block - stay with the entry-per-thread form: measured
   // 19-25 us there against 22-51 us for the row form; wide rows 16-23 us against 23-38 us)
-  if (Ch <= 48 && C <= 512 && C > 128) {
-    const int chp = (Ch + 3) & ~3, heads = C / Ch;
-    const size_t lds2 = (size_t)FA_TOK * (C + heads * chp) * sizeof(float);
+  if (fa_row_form(C, Ch)) {
+    const int chp = (Ch + 3) & ~3;
+    const size_t lds2 = fa_context_rows_lds(C, Ch);
+    if (lds2 > FA_LDS_DEFAULT) return BBD_E_BADARG;      // 24 instantiations: none asks for the opt-in (see the predicate)
     const dim3 block((unsigned)((C + 63) / 64 * 64));
 #define BBD_FAR(P) hipLaunchKernelGGL((fa_context_rows_kernel<SOFTMAX, P>), grid, block, lds2, st, qkv, bsrc, brow, kmax, krsum, part, N, C, Ch, seg_tokens)
     switch (chp) {
@@ -618,15 +651,23 @@ void fa_launch_context(dim3 grid, size_t lds, hipStream_t st, const float* qkv, 
       case 36: BBD_FAR(36); break;  case 40: BBD_FAR(40); break;  case 44: BBD_FAR(44); break;  default: BBD_FAR(48); break;
     }
 #undef BBD_FAR
-    return;
+    return 0;
   }
   const int nacc = (C * Ch + NT - 1) / NT;
-#define BBD_FA(M) hipLaunchKernelGGL((fa_context_kernel<SOFTMAX, M>), grid, dim3(NT), lds, st, qkv, bsrc, brow, kmax, krsum, part, N, C, Ch, seg_tokens)
+  const size_t lds = fa_context_lds(C);
+#define BBD_FA(M)                                                                                                        \
+  do {                                                                                                                   \
+    static size_t granted = 0;                                                                                           \
+    if (!fa_lds_granted(fa_context_kernel<SOFTMAX, M>, lds, &granted)) return BBD_E_BADARG;                              \
+    hipLaunchKernelGGL((fa_context_kernel<SOFTMAX, M>), grid, dim3(NT), lds, st, qkv, bsrc, brow, kmax, krsum, part, N, C, \
+                       Ch, seg_tokens);                                                                                  \
+  } while (0)
   if (nacc <= 2) BBD_FA(2);
   else if (nacc <= 8) BBD_FA(8);
   else if (nacc <= 24) BBD_FA(24);
   else BBD_FA(48);
 #undef BBD_FA
+  return 0;
 }
 
 /* segments of tokens: enough workgroups to fill the chip, at least FA_TOK tokens each */
@@ -763,7 +804,16 @@ int bbd_dwconv_tokens_groups_wgrad(const float* x, int x_row, const float* grad_
 
 int bbd_factor_att_segments(int B, int N) { return fa_segments(B, N); }
 int bbd_factor_att_supported(int C, int Ch) {
-  return C > 0 && Ch > 0 && C % Ch == 0 && (long)C * Ch <= (long)NT * FA_MAXO && C <= 1024;
+  if (!(C > 0 && Ch > 0 && C % Ch == 0 && (long)C * Ch <= (long)NT * FA_MAXO && C <= 1024)) return 0;
+  // every launch's dynamic LDS fits a workgroup (the launches opt in above 64 KiB) ...
+  if (fa_apply_lds(C, Ch) > FA_LDS_MAX || fa_bwd_lds(C, Ch) > FA_LDS_MAX) return 0;
+  // ... and the context launch the shape takes.  The row form (block = C rounded up to whole waves <= 512 threads) is
+  // held to the default 64 KiB, since its 24 instantiations would each need an opt-in of their own: 64 (C + heads * CHP)
+  // bytes, so a shape is refused when C + heads * CHP > 1024.  Without padding (Ch a multiple of 4) that is 2 C <= 1024,
+  // never refused; what goes beyond are wide rows whose heads are padded: (256,1) 81 920 B, (512,2) 98 304 B, and also
+  // (510,5) 84 864 B, (504,6) 75 264 B.  No model has such a shape; they take the eager path.  The entry form opts in.
+  if (fa_row_form(C, Ch)) return fa_context_rows_lds(C, Ch) <= FA_LDS_DEFAULT;
+  return fa_context_lds(C) <= FA_LDS_MAX;
 }
 
 int bbd_factor_att_fwd(const float* qkv, const float* convv, float* kmax, float* krsum, float* ctxs, float* scratch,
@@ -778,13 +828,15 @@ int bbd_factor_att_fwd(const float* qkv, const float* convv, float* kmax, float*
   hipLaunchKernelGGL(fa_kstats_kernel, dim3(nseg, B), dim3(NT), 0, st, qkv, pm, ps, N, C, seg_tokens);
   hipLaunchKernelGGL(fa_kstats_combine_kernel, dim3((unsigned)((B * C + 63) / 64)), dim3(NT), 0, st, pm, ps, kmax,
                      krsum, nseg, C, B * C);
-  fa_launch_context<true>(dim3(nseg, B), (size_t)2 * FA_TOK * C * sizeof(float), st, qkv, qkv + 2 * C, 3 * C, kmax, krsum,
-                          part, N, C, Ch, seg_tokens);
+  if (fa_launch_context<true>(dim3(nseg, B), st, qkv, qkv + 2 * C, 3 * C, kmax, krsum, part, N, C, Ch, seg_tokens))
+    return BBD_E_BADARG;
   hipLaunchKernelGGL(fa_context_reduce_kernel, dim3((unsigned)(((long)B * nout + 63) / 64)), dim3(NT), 0, st, part,
                      ctxs, nseg, nout, B * nout, (float)scale);
-  const int tpb = 8;
-  hipLaunchKernelGGL(fa_apply_kernel, dim3((unsigned)((N + tpb - 1) / tpb), B), dim3(NT),
-                     (size_t)(nout + tpb * C + C) * sizeof(float), st, qkv, ctxs, convv, out, N, C, Ch, tpb);
+  static size_t granted = 0;
+  const size_t lds = fa_apply_lds(C, Ch);
+  if (!fa_lds_granted(fa_apply_kernel, lds, &granted)) return BBD_E_BADARG;
+  hipLaunchKernelGGL(fa_apply_kernel, dim3((unsigned)((N + FA_TPB - 1) / FA_TPB), B), dim3(NT), lds, st, qkv, ctxs, convv,
+                     out, N, C, Ch, FA_TPB);
   return launch_status();
 }
 
@@ -802,22 +854,15 @@ int bbd_factor_att_bwd(const float* qkv, const float* convv, const float* kmax, 
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int nseg = fa_segments(B, N), seg_tokens = (N + nseg - 1) / nseg, nout = C * Ch;
   float* part = scratch + 2L * B * nseg * C;
-  fa_launch_context<false>(dim3(nseg, B), (size_t)2 * FA_TOK * C * sizeof(float), st, qkv, grad_out, C, kmax, krsum, part,
-                           N, C, Ch, seg_tokens);
+  if (fa_launch_context<false>(dim3(nseg, B), st, qkv, grad_out, C, kmax, krsum, part, N, C, Ch, seg_tokens))
+    return BBD_E_BADARG;
   hipLaunchKernelGGL(fa_context_reduce_kernel, dim3((unsigned)(((long)B * nout + 63) / 64)), dim3(NT), 0, st, part,
                      dctx, nseg, nout, B * nout, (float)scale);
-  const int tpb = 8, Chp = Ch | 1;
-  const size_t lds = (size_t)(2 * C * Chp + C + 3 * tpb * C + C) * sizeof(float);
-  if (lds > 64 * 1024) {      // up to 114 KB for C = 288, Ch = 36: above the default dynamic-LDS limit
-    static size_t granted = 0;
-    if (lds > granted) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(fa_bwd_token_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return BBD_E_BADARG;
-      granted = lds;
-    }
-  }
-  hipLaunchKernelGGL(fa_bwd_token_kernel, dim3((unsigned)((N + tpb - 1) / tpb), B), dim3(NT), lds, st, qkv, ctxs, dctx,
-                     convv, grad_out, kmax, krsum, grad_qkv, grad_convv, N, C, Ch, tpb, (float)(1.0 / scale));
+  static size_t granted = 0;      // up to 114 KB for C = 288, Ch = 36: above the default dynamic-LDS limit
+  const size_t lds = fa_bwd_lds(C, Ch);
+  if (!fa_lds_granted(fa_bwd_token_kernel, lds, &granted)) return BBD_E_BADARG;
+  hipLaunchKernelGGL(fa_bwd_token_kernel, dim3((unsigned)((N + FA_TPB - 1) / FA_TPB), B), dim3(NT), lds, st, qkv, ctxs, dctx,
+                     convv, grad_out, kmax, krsum, grad_qkv, grad_convv, N, C, Ch, FA_TPB, (float)(1.0 / scale));
   return launch_status();
 }
 

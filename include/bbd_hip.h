@@ -680,7 +680,11 @@ int bbd_colsum(const float* x, float* partial, float* out, long rows, int C, voi
  *   bwd : grad_out [B,N,C] -> grad_qkv [B,N,3C] (dq | dk | dv), grad_convv [B,N,C]; dctx = work buffer
  *         [B, h, Ch, Ch].  scratch: bbd_factor_att_scratch_floats(B,N,C,Ch) floats for both calls.
  *   Deterministic (per-token-segment partial sums combined in fixed order).  Supported shapes:
- *   bbd_factor_att_supported(C, Ch) != 0 (C*Ch <= 12288: MPViT tiny / xsmall / small).                    */
+ *   bbd_factor_att_supported(C, Ch) != 0: Ch divides C, C <= 1024, C*Ch <= 12288, and the dynamic LDS of each of the
+ *   four launches (context in the form the shape takes, output, backward) fits a workgroup (160 KiB; the launches
+ *   opt in above 64 KiB, the row-per-thread context form - 128 < C <= 512, Ch <= 48 - stays within 64 KiB).  True for
+ *   every stage of MPViT tiny / xsmall / small and up to (512,16), (576,18); false e.g. for (768,16), (1024,12),
+ *   (256,1), (512,2), (510,5), (504,6).  Both calls return BBD_E_BADARG for a shape the predicate refuses.        */
 int bbd_factor_att_supported(int C, int Ch);
 int bbd_factor_att_segments(int B, int N);
 long bbd_factor_att_scratch_floats(int B, int N, int C, int Ch);
