@@ -20,7 +20,7 @@ PROJ_STRIDE = 24
 KIND_WARP, KIND_IDENT, FLAG_NO_POSE_GRAD = 0, 1, 0x100
 COMPOSE_STRIDE, COMPOSE_ERROR, COMPOSE_REPLACE = 12, 1, 2
 PAIR_SHIFT = 16        # bits 16-23 of bbd_cand_t.kind: 1 + index of the pass partner (hint), 0 = none
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 _p = ctypes.c_void_p
 _i = ctypes.c_int
@@ -77,6 +77,9 @@ SIGNATURES = {
     "bbd_train_panel_scratch_ints": [_i],
     "bbd_train_panel": [_p] * 6 + [_i] * 6 + [_p],
     "bbd_argmin_hist": [_p, _p, _i, _i, _p],
+    "bbd_gt_viz_scratch_ints": [_i],
+    "bbd_gt_viz": [_p] * 6 + [_i, _d, _p],
+    "bbd_error_map": [_p] * 8 + [_i, _i, _i, _d, _d, _d, _d, _i, _i, _p],
     "bbd_resample_h_u8": [_p, _p, _p, _i, _i, _p, _p, _i, _p],
     "bbd_resample_v_u8": [_p, _p, _p, _i, _i, _i, _p, _p, _i, _p],
     "bbd_color_jitter_u8": [_p, _p, _p, _i, _i, _i, _p, _p],
@@ -129,6 +132,7 @@ PANEL_DESC, PANEL_COLOR, PANEL_WARP, PANEL_SCALAR, PANEL_ARGMIN, PANEL_LUT_ROWS 
 VELO_DESC, VELO_VEL_DEPTH = 8, 1
 SYNS_OUT, SYNS_CLOUD_OUT, SYNS_RAYS_PIXEL = 8, 8, 8
 EVAL_PRED_IS_DISP, EVAL_MEDIAN_MIDPOINT, EVAL_NO_MEDIAN_SCALING = 1, 2, 4
+ERROR_MAP_MAX_RADIUS = 4
 
 
 class BbdError(RuntimeError):
@@ -200,6 +204,9 @@ class HipLibrary:
 
     def train_panel_scratch_ints(self, n_tiles):
         return self._dll.bbd_train_panel_scratch_ints(n_tiles)
+
+    def gt_viz_scratch_ints(self, n):
+        return self._dll.bbd_gt_viz_scratch_ints(n)
 
     def velo_depth_scratch_ints(self, total_pixels, n_frames):
         return self._dll.bbd_velo_depth_scratch_ints(total_pixels, n_frames)

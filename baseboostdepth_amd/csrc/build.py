@@ -14,12 +14,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRCS = [os.path.join(HERE, "bbd_kernels.hip"), os.path.join(HERE, "bbd_eval.hip"),
         os.path.join(HERE, "bbd_image.hip"), os.path.join(HERE, "bbd_nn.hip"), os.path.join(HERE, "bbd_vit.hip"), os.path.join(HERE, "bbd_pose.hip"), os.path.join(HERE, "bbd_tokens.hip"), os.path.join(HERE, "bbd_util.hip"),
         os.path.join(HERE, "bbd_viz.hip"), os.path.join(HERE, "bbd_velo.hip"), os.path.join(HERE, "bbd_syns.hip"),
-        os.path.join(HERE, "bbd_odom.hip"), os.path.join(HERE, "bbd_postproc.hip"), os.path.join(HERE, "bbd_panel.hip")]
+        os.path.join(HERE, "bbd_odom.hip"), os.path.join(HERE, "bbd_postproc.hip"), os.path.join(HERE, "bbd_panel.hip"),
+        os.path.join(HERE, "bbd_compare.hip")]
 OUT = os.path.join(HERE, "libbbd_hip.so")
 DEPS = SRCS + [os.path.abspath(__file__), os.path.join(HERE, "bbd_math.h"), os.path.join(HERE, "bbd_image_math.h"), os.path.join(HERE, "bbd_viz_math.h"),
                os.path.join(HERE, "bbd_velo_math.h"), os.path.join(HERE, "bbd_eval_math.h"), os.path.join(HERE, "bbd_syns_math.h"),
                os.path.join(HERE, "bbd_odom_math.h"), os.path.join(HERE, "bbd_postproc_math.h"),
-               os.path.join(HERE, "bbd_panel_math.h"),
+               os.path.join(HERE, "bbd_panel_math.h"), os.path.join(HERE, "bbd_compare_math.h"),
                os.path.join(HERE, "..", "..", "include", "bbd_hip.h")]
 # -fno-slp-vectorize: hipcc otherwise SLP-packs neighbouring scalar fp32 adds / multiplies into v_pk_add/mul_f32 and
 # pays for it in v_mov register shuffles (129 moves in the forward's SSIM phase): measured forward 0.222 -> 0.208 ms,

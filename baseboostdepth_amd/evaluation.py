@@ -59,6 +59,7 @@ class GroundTruthSet:
         flat = np.concatenate([m.ravel() for m in maps]) if maps else np.zeros(0, np.float32)
         self.shapes = [m.shape for m in maps]
         self.buffer = torch.from_numpy(flat).to(device)
+        self.desc_host = desc                   # the same rows on the host (ops.gt_viz / ops.error_map rebase them)
         self.desc = torch.from_numpy(desc).to(device)
 
     @classmethod
@@ -79,6 +80,7 @@ class GroundTruthSet:
         self.edges = None
         self.shapes = shapes
         self.buffer = buffer
+        self.desc_host = desc
         self.desc = torch.from_numpy(desc).to(buffer.device)
         return self
 

@@ -68,9 +68,9 @@ class DepthPredictor:
         decoder.load_state_dict(torch.load(os.path.join(folder, "depth.pth"), map_location=device), strict=False)
         return cls(encoder, decoder, height, width, device, **kw)
 
-    def prepare(self, images):
-        """uint8 HWC RGB arrays of any sizes -> fp32 [n,3,feed_h,feed_w] on the device, bit-equal to
-        `ToTensor()(pil.resize((feed_w, feed_h), LANCZOS))` of each: one upload, then the image kernels."""
+    def upload(self, images):
+        """uint8 HWC RGB arrays of any sizes -> (device buffer holding them back to back, jobs = [(byte offset, h, w,
+        False)] as `ImagePipeline.resize` takes them): the one upload of a batch."""
         arrays = [np.ascontiguousarray(im) for im in images]
         jobs, off = [], 0
         for a in arrays:
@@ -81,13 +81,21 @@ class DepthPredictor:
         flat = host.numpy()
         for a, (o, _, _, _) in zip(arrays, jobs):
             flat[o:o + a.size] = a.reshape(-1)
-        src = host.to(self.device, non_blocking=True)
-        n = len(arrays)
+        return host.to(self.device, non_blocking=True), jobs
+
+    def prepare_uploaded(self, src, jobs):
+        """The image kernels on an uploaded batch (`upload`): fp32 [n,3,feed_h,feed_w]."""
+        n = len(jobs)
         u8 = self.pipe.resize(src, jobs, self.feed_height, self.feed_width)
         x = torch.empty(n, 3, self.feed_height, self.feed_width, dtype=torch.float32, device=self.device)
         self.pipe.to_float(u8, list(range(n)), x, list(range(n)))
         self.pipe.flush()
         return x
+
+    def prepare(self, images):
+        """uint8 HWC RGB arrays of any sizes -> fp32 [n,3,feed_h,feed_w] on the device, bit-equal to
+        `ToTensor()(pil.resize((feed_w, feed_h), LANCZOS))` of each: one upload, then the image kernels."""
+        return self.prepare_uploaded(*self.upload(images))
 
     def disparity(self, x):
         """Network output ("disp", 0) for prepared inputs, in batches of at most `batch_size`.  Convolutions are asked

@@ -1521,14 +1521,17 @@ def viz_buffer(views):
     return views[0]._base
 
 
-def disp_viz(disp, sizes, min_depth=0.1, max_depth=80.0, percentile=95.0, want_float=False, backend=None):
+def disp_viz(disp, sizes, min_depth=0.1, max_depth=80.0, percentile=95.0, want_float=False, backend=None, raw=False):
     """test_simple.py:135-148 for a batch: network disparities `disp` [n,1,h,w] (sigmoid output) -> per image the
     magma-coloured scaled disparity at its original size `sizes[i] = (H0, W0)` (ragged), normalised between its minimum
     and its `percentile`-th percentile (np.percentile, exact).  One `bbd_disp_viz` call, no host synchronisation.
 
     Returns (colour, floats, stats): `colour` a list of uint8 [H0,W0,3] views into ONE buffer (`colour[0]._base` - a
     single copy brings all of them to the host), `floats` a list of fp32 [H0,W0] views of the scaled disparity (None
-    unless `want_float`), `stats` fp32 [n,4] = vmin, vmax and the two order statistics vmax was interpolated from."""
+    unless `want_float`), `stats` fp32 [n,4] = vmin, vmax and the two order statistics vmax was interpolated from.
+
+    `raw=True` is validation.py:205-212 instead: the network output itself (s = 0 + 1 * d), normalised between its
+    minimum and its maximum (the 100th percentile); `min_depth`, `max_depth` and `percentile` are not used."""
     backend = backend or default_backend()
     disp = disp.detach()
     if disp.dim() == 4:
@@ -1552,7 +1555,7 @@ def disp_viz(disp, sizes, min_depth=0.1, max_depth=80.0, percentile=95.0, want_f
     stats = torch.empty(n, 4, dtype=torch.float32, device=dev)
     scratch = torch.empty(backend.lib.disp_viz_scratch_ints(n), dtype=torch.int32, device=dev)
     backend.run("bbd_disp_viz", disp, ptr(disp), ptr(desc), ptr(magma_lut(dev)), ptr(out), ptr(outf), ptr(stats),
-                ptr(scratch), n, h, w, 1.0 / max_depth, 1.0 / min_depth, float(percentile))
+                ptr(scratch), n, h, w, *((0.0, 1.0, 100.0) if raw else (1.0 / max_depth, 1.0 / min_depth, float(percentile))))
     colour, floats = [], ([] if want_float else None)
     for (lo, hi, H0, W0) in rows:
         o = (lo & 0xFFFFFFFF) | (hi << 32)
@@ -1560,6 +1563,94 @@ def disp_viz(disp, sizes, min_depth=0.1, max_depth=80.0, percentile=95.0, want_f
         if want_float:
             floats.append(outf[o:o + H0 * W0].view(H0, W0))
     return colour, floats, stats
+
+
+# ---------------------------------------------------------------------------- comparison sheets (validation.py)
+class _GtBatch:
+    """Maps `indices` of a `GroundTruthSet` as one call sees them: the set's descriptor rows with their offsets rebased to
+    the first element any of the maps uses, so that the pictures (written at 3x the maps' offsets) need a buffer of the
+    batch's span only.  Consecutive indices - a batch of a split - span exactly their own pixels."""
+
+    def __init__(self, gts, indices):
+        self.idx = [int(i) for i in indices]
+        assert self.idx and all(0 <= i < len(gts) for i in self.idx)
+        host = gts.desc_host[self.idx].astype("int64")
+        offs = (host[:, 0] & 0xFFFFFFFF) | (host[:, 1] << 32)
+        self.shapes = [tuple(int(v) for v in gts.shapes[i]) for i in self.idx]
+        sizes = [gh * gw for gh, gw in self.shapes]
+        self.base = int(offs.min())
+        self.rel = [int(o) - self.base for o in offs]
+        self.span = max(r + s for r, s in zip(self.rel, sizes))
+        rows = host.copy()
+        rows[:, 0] = [r & 0x7FFFFFFF | (-(r >> 31 & 1) << 31) for r in self.rel]
+        rows[:, 1] = [r >> 32 for r in self.rel]
+        desc = torch.from_numpy(rows.astype("int32"))
+        dev = gts.buffer.device
+        self.desc = desc.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else desc
+        self.gt = gts.buffer[self.base:]
+
+    def pictures(self, buf):
+        return [buf[3 * r:3 * (r + gh * gw)].view(gh, gw, 3) for r, (gh, gw) in zip(self.rel, self.shapes)]
+
+    def planes(self, buf):
+        return [buf[r:r + gh * gw].view(gh, gw) for r, (gh, gw) in zip(self.rel, self.shapes)]
+
+
+def gt_viz(gts, indices, max_inv=80.0, backend=None):
+    """validation.py:250-254 for maps `indices` of the `GroundTruthSet` `gts`: the magma-coloured inverse depth
+    (1 / gt, values above `max_inv` zeroed) normalised between its minimum and maximum.  One `bbd_gt_viz` call, no host
+    synchronisation.  Returns (pictures, stats): uint8 [GH,GW,3] views into ONE buffer (`viz_buffer(pictures)`), picture
+    i at 3x the offset map i has from the first map of the batch, and fp32 [n,2] = vmin, vmax."""
+    backend = backend or default_backend()
+    b = _GtBatch(gts, indices)
+    backend._check(gts.buffer)
+    dev, n = gts.buffer.device, len(b.idx)
+    out = torch.empty(3 * b.span, dtype=torch.uint8, device=dev)
+    stats = torch.empty(n, 2, dtype=torch.float32, device=dev)
+    scratch = torch.empty(backend.lib.gt_viz_scratch_ints(n), dtype=torch.int32, device=dev)
+    backend.run("bbd_gt_viz", out, ptr(b.gt), ptr(b.desc), ptr(magma_lut(dev)), ptr(out), ptr(stats), ptr(scratch), n,
+                float(max_inv))
+    return b.pictures(out), stats
+
+
+def error_map(pred_disp, gts, indices, rows, images=None, min_depth=0.1, max_depth=80.0, scale_factor=1.0, err_max=0.5,
+              radius=2, median_scaling=True, want_float=False, backend=None):
+    """Where a model is wrong: `pred_disp` ([n,1,h,w] or [n,h,w]) is the scaled disparity `evaluation.depth_metrics` was
+    given with `pred_is_disp=True` and `rows` that call's output.  Every valid ground-truth pixel (the pixels the metrics
+    score) carries its abs_rel summand |gt - pred| / gt; every output pixel shows, in magma between 0 and `err_max`, the
+    largest one within Chebyshev distance `radius` (0-4), and where there is none the darkened grey of `images` (uint8
+    HWC at the ground-truth sizes: a list, or ONE buffer laid out like the returned pictures) or black.  One
+    `bbd_error_map` call, no host synchronisation.  Returns (pictures, planes): uint8 [GH,GW,3] views into one buffer as
+    `gt_viz` returns them, and - with `want_float` - fp32 [GH,GW] views holding the error at valid pixels and NaN
+    elsewhere (None otherwise)."""
+    backend = backend or default_backend()
+    if not 0 <= int(radius) <= _lib.ERROR_MAP_MAX_RADIUS:
+        raise ValueError("error_map: radius must be 0 ... %d, got %r" % (_lib.ERROR_MAP_MAX_RADIUS, radius))
+    pred = pred_disp.detach()
+    if pred.dim() == 4:
+        assert pred.shape[1] == 1
+        pred = pred[:, 0]
+    pred = pred.contiguous().float()
+    b = _GtBatch(gts, indices)
+    n, h, w = pred.shape
+    assert n == len(b.idx)
+    assert rows.dtype == torch.float32 and tuple(rows.shape) == (n, _lib.EVAL_OUT) and rows.is_contiguous()
+    dev = pred.device
+    if images is not None and not torch.is_tensor(images):
+        packed = torch.zeros(3 * b.span, dtype=torch.uint8, device=dev)
+        for view, im in zip(b.pictures(packed), images):
+            assert im.dtype == torch.uint8 and tuple(im.shape) == tuple(view.shape), "pictures are HWC uint8 at the ground-truth size"
+            view.copy_(im)
+        images = packed
+    if images is not None:
+        assert images.dtype == torch.uint8 and images.dim() == 1 and images.numel() >= 3 * b.span and images.is_contiguous()
+    backend._check(pred, gts.buffer, rows, images)
+    out = torch.empty(3 * b.span, dtype=torch.uint8, device=dev)
+    outf = torch.empty(b.span, dtype=torch.float32, device=dev) if want_float else None
+    backend.run("bbd_error_map", pred, ptr(pred), ptr(b.gt), ptr(b.desc), ptr(rows), ptr(images), ptr(magma_lut(dev)),
+                ptr(out), ptr(outf), n, h, w, float(min_depth), float(max_depth), float(scale_factor), float(err_max),
+                int(radius), 0 if median_scaling else _lib.EVAL_NO_MEDIAN_SCALING)
+    return b.pictures(out), (b.planes(outf) if want_float else None)
 
 
 # ---------------------------------------------------------------------------- Velodyne depth maps

@@ -39,7 +39,7 @@ extern "C" {
  * 10 = bbd_syns_* / bbd_chamfer_nn (SYNS-Patches evaluation: edge and point-cloud metrics);
  * 11 = bbd_pose_ate (KITTI odometry evaluation: chained poses, local ground truth, trajectory error);
  * 12 = bbd_post_process_disp (depth evaluation: flip post-processing of the predicted disparities). */
-#define BBD_ABI_VERSION 12
+#define BBD_ABI_VERSION 13
 
 /* Source frames live in separate tensors, one per frame id (inputs[("color", f, 0)],
  * trainer.py:428).  A "slot" indexes a host array of their base pointers. */
@@ -354,6 +354,46 @@ int bbd_train_panel(const int32_t* desc, const float* pose, const uint8_t* lut, 
  * counted.  counts int32 [B, BBD_MAX_CAND] is zeroed on `stream` by the call; one launch, integer atomics (exact).
  * B <= 65535. */
 int bbd_argmin_hist(const uint8_t* argmin, int32_t* counts, int B, int n_px, void* stream);
+
+/* Checkpoint comparison sheets (csrc/bbd_compare.hip, validation.py): the two pictures that are not a disparity.  Both
+ * take a ragged batch of n ground-truth maps described by BBD_EVAL_DESC rows (offset lo, hi in elements of `gt`, GH, GW,
+ * crop window r0, r1, c0, c1 - the table of bbd_depth_metrics) and write picture i as uint8 RGB [GH, GW, 3] at
+ * out_u8 + 3 * offset_i: the maps' packing is the pictures' packing.  A picture that starts on a 4-byte boundary gets
+ * 12-byte packed stores, any other byte stores.  lut is magma, uint8 [256,3] (baseboostdepth_amd/magma_lut.hex).
+ *
+ * bbd_gt_viz - the colour-mapped ground truth (validation.py:250-254), for every pixel g of map i:
+ *   v    = 1.0f / g                         IEEE float32 division: a zero (no LiDAR return) gives +inf
+ *   v    = v > max_inv ? 0.0f : v           the reference's value of max_inv is 80
+ *   vmin, vmax = minimum / maximum of v over the whole map, NaNs skipped (exact: integer maxima of order keys)
+ *   rgb  = lut[bbd_viz_lut_index(v, vmin, vmax)]          vmax == vmin and NaN take entry 0
+ * stats[i] = {vmin, vmax} (NaN, NaN for a map of NaNs or without pixels).  The crop window is not used.  scratch holds
+ * bbd_gt_viz_scratch_ints(n) int32 and needs no initialisation.  Two launches (partial extrema; the colouring), no
+ * atomics, no allocation, no host synchronisation: identical calls give identical bytes.
+ *
+ * bbd_error_map - where a model is wrong.  pred [n,h,w] is the scaled disparity bbd_depth_metrics was given with
+ * BBD_EVAL_PRED_IS_DISP, rows [n, BBD_EVAL_OUT] that call's output (ratio and count are read on the device).  A pixel
+ * (y, x) of map i is VALID when it lies inside the row's crop window and min_depth < g < max_depth in float32 - the
+ * pixels bbd_depth_metrics scores - and its error is that kernel's abs_rel summand:
+ *   p = bbd_eval_resample(pred[i], ..., BBD_EVAL_PRED_IS_DISP, y, x)         cv2-style resize, 1 / x, * scale_factor
+ *   p *= ratio  unless flags has BBD_EVAL_NO_MEDIAN_SCALING;  p = min(max(p, min_depth), max_depth)
+ *   e = fabsf(g - p) / g
+ * Every output pixel takes the MAXIMUM e over the valid pixels within Chebyshev distance `radius` (0 ..
+ * BBD_ERROR_MAP_MAX_RADIUS; neighbours outside the map do not exist) - a gather, so nothing depends on order - and is
+ * coloured lut[bbd_viz_lut_index(e_max, 0.0f, err_max)].  A pixel without a valid neighbour takes (r + g + b) / 6
+ * (integer division) of pixel (y, x) of images + 3 * offset_i (uint8 HWC at the ground-truth size) in all three
+ * channels, or black when images is NULL.  A row whose count is 0 is all background.  out_float (may be NULL) receives
+ * at out_float + offset_i the error e of every valid pixel and the quiet NaN 0x7fc00000 elsewhere.  One launch, no
+ * scratch, no atomics.  flags may hold BBD_EVAL_NO_MEDIAN_SCALING only.
+ *
+ * Both return BBD_E_BADARG and launch nothing for a NULL pointer (other than the optional ones), n outside
+ * [1, 65535], h or w below 1, a radius outside its range or an unknown flag. */
+#define BBD_ERROR_MAP_MAX_RADIUS 4
+int bbd_gt_viz_scratch_ints(int n);
+int bbd_gt_viz(const float* gt, const int32_t* desc, const uint8_t* lut, uint8_t* out_u8, float* stats, int32_t* scratch,
+               int n, double max_inv, void* stream);
+int bbd_error_map(const float* pred, const float* gt, const int32_t* desc, const float* rows, const uint8_t* images,
+                  const uint8_t* lut, uint8_t* out_u8, float* out_float, int n, int h, int w, double min_depth,
+                  double max_depth, double scale_factor, double err_max, int radius, int flags, void* stream);
 
 /* Ground-truth depth maps from Velodyne scans (kitti_utils.py:46-98, generate_depth_map), a ragged batch of n_frames
  * frames per call, written straight into a packed float32 buffer such as evaluation.GroundTruthSet keeps.
