@@ -20,48 +20,23 @@
 #include "bbd_viz_math.h"
 #include "bbd_panel_math.h"
 #include "bbd_compare_math.h"
+#include "bbd_device_util.h"
 
 namespace {
 
 constexpr int CT = 256;              // threads per workgroup
-constexpr int CW = CT / 64;          // waves
-constexpr int PARTS = 16;            // partial extrema per map
+constexpr int PARTS = BBD_EXTREMA_PARTS;   // partial extrema per map
 constexpr int CTILES = 128;          // workgroups per map in the colouring launches (grid-stride beyond)
 
-struct Map {
-  size_t off;
-  int GH, GW, r0, r1, c0, c1;
+struct Map : BbdEvalRow {
   uint32_t npx;
 };
 
 __device__ __forceinline__ Map load_map(const int32_t* desc, int i) {
-  const int32_t* d = desc + (size_t)i * BBD_EVAL_DESC;
   Map m;
-  m.off = (size_t)(uint32_t)d[0] | ((size_t)(uint32_t)d[1] << 32);
-  m.GH = d[2]; m.GW = d[3]; m.r0 = d[4]; m.r1 = d[5]; m.c0 = d[6]; m.c1 = d[7];
+  static_cast<BbdEvalRow&>(m) = bbd_eval_row(desc, i);
   m.npx = m.GH > 0 && m.GW > 0 ? (uint32_t)m.GH * (uint32_t)m.GW : 0u;
   return m;
-}
-
-// Four colours (r | g << 8 | b << 16) of pixels i0 .. i0 + cnt - 1 of a picture that starts at `out`.
-__device__ __forceinline__ void store_quad(uint8_t* out, bool packed, uint32_t i0, uint32_t cnt, const uint32_t c[4]) {
-  if (packed && cnt == 4u) {                // 12 bytes per lane, contiguous across the wave
-    uint32_t* o = reinterpret_cast<uint32_t*>(out + (size_t)i0 * 3);
-    o[0] = c[0] | (c[1] << 24);
-    o[1] = (c[1] >> 8) | (c[2] << 16);
-    o[2] = (c[2] >> 16) | (c[3] << 8);
-  } else {
-    for (uint32_t k = 0; k < cnt; ++k) {
-      uint8_t* o = out + (size_t)(i0 + k) * 3;
-      o[0] = (uint8_t)c[k]; o[1] = (uint8_t)(c[k] >> 8); o[2] = (uint8_t)(c[k] >> 16);
-    }
-  }
-}
-
-__device__ __forceinline__ void load_lut(uint32_t* lut, const uint8_t* src) {
-  for (int i = threadIdx.x; i < 256; i += CT)
-    lut[i] = (uint32_t)src[3 * i] | ((uint32_t)src[3 * i + 1] << 8) | ((uint32_t)src[3 * i + 2] << 16);
-  __syncthreads();
 }
 
 struct GtArgs {
@@ -75,24 +50,11 @@ struct GtArgs {
 };
 
 __global__ __launch_bounds__(CT) void gt_extrema_kernel(GtArgs a) {
-  __shared__ uint32_t sh[2 * CW];
-  const int img = blockIdx.y, part = blockIdx.x, tid = threadIdx.x;
+  const int img = blockIdx.y;
   const Map m = load_map(a.desc, img);
   const float* gt = a.gt + m.off;
-  uint32_t inv_min = 0u, max_key = 0u;
-  for (uint32_t i = (uint32_t)part * CT + tid; i < m.npx; i += (uint32_t)PARTS * CT)
-    bbd_panel_minmax_update(bbd_compare_gt_inverse(gt[i], a.max_inv), &inv_min, &max_key);
-  for (int o = 32; o > 0; o >>= 1) {
-    inv_min = max(inv_min, (uint32_t)__shfl_down(inv_min, o, 64));
-    max_key = max(max_key, (uint32_t)__shfl_down(max_key, o, 64));
-  }
-  if ((tid & 63) == 0) { sh[2 * (tid >> 6)] = inv_min; sh[2 * (tid >> 6) + 1] = max_key; }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < CW; ++w) { inv_min = max(inv_min, sh[2 * w]); max_key = max(max_key, sh[2 * w + 1]); }
-    uint32_t* sc = a.scratch + ((size_t)img * PARTS + part) * 2;
-    sc[0] = inv_min; sc[1] = max_key;
-  }
+  extrema_part<CT>(m.npx, [&](uint32_t i) { return bbd_compare_gt_inverse(gt[i], a.max_inv); },
+                   a.scratch + ((size_t)img * PARTS + blockIdx.x) * 2);
 }
 
 __global__ __launch_bounds__(CT) void gt_colour_kernel(GtArgs a) {
@@ -101,12 +63,9 @@ __global__ __launch_bounds__(CT) void gt_colour_kernel(GtArgs a) {
   const Map m = load_map(a.desc, img);
   const uint32_t nquad = (m.npx + 3u) / 4u;
   if (tile > 0 && (uint64_t)tile * CT >= nquad) return;      // uniform: no pixel here (tile 0 still writes the stats)
-  load_lut(lut, a.lut);
-  const uint32_t* sc = a.scratch + (size_t)img * PARTS * 2;
-  uint32_t inv_min = 0u, max_key = 0u;
-  for (int p = 0; p < PARTS; ++p) { inv_min = max(inv_min, sc[2 * p]); max_key = max(max_key, sc[2 * p + 1]); }
+  stage_lut<256, CT>(lut, a.lut);
   float vmin, vmax;
-  bbd_panel_minmax_values(inv_min, max_key, &vmin, &vmax);
+  extrema_combine(a.scratch + (size_t)img * PARTS * 2, &vmin, &vmax);
   if (tile == 0 && tid == 0) { a.stats[(size_t)img * 2] = vmin; a.stats[(size_t)img * 2 + 1] = vmax; }
   const float* gt = a.gt + m.off;
   uint8_t* out = a.out + 3 * m.off;
@@ -116,7 +75,7 @@ __global__ __launch_bounds__(CT) void gt_colour_kernel(GtArgs a) {
     uint32_t c[4] = {0u, 0u, 0u, 0u};
     for (uint32_t k = 0; k < cnt; ++k)
       c[k] = lut[bbd_viz_lut_index(bbd_compare_gt_inverse(gt[i0 + k], a.max_inv), vmin, vmax)];
-    store_quad(out, packed, i0, cnt, c);
+    store_quad(out + (size_t)i0 * 3, packed, cnt, c);
   }
 }
 
@@ -139,7 +98,7 @@ __global__ __launch_bounds__(CT) void error_map_kernel(ErrArgs a) {
   const Map m = load_map(a.desc, img);
   const uint32_t nquad = (m.npx + 3u) / 4u;
   if ((uint64_t)tile * CT >= nquad) return;                  // uniform
-  load_lut(lut, a.lut);
+  stage_lut<256, CT>(lut, a.lut);
   const float* row = a.rows + (size_t)img * BBD_EVAL_OUT;
   const bool scored = row[10] != 0.0f;                       // count == 0: nothing was scored, all background
   BbdCompareMap cm;
@@ -168,7 +127,7 @@ __global__ __launch_bounds__(CT) void error_map_kernel(ErrArgs a) {
       else if (pic) c[k] = bbd_compare_grey(pic + (size_t)i * 3);
       if (++x == m.GW) { x = 0; ++y; }
     }
-    store_quad(out, packed, i0, cnt, c);
+    store_quad(out + (size_t)i0 * 3, packed, cnt, c);
   }
 }
 
@@ -185,8 +144,7 @@ extern "C" int bbd_gt_viz(const float* gt, const int32_t* desc, const uint8_t* l
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(gt_extrema_kernel, dim3(PARTS, (unsigned)n), dim3(CT), 0, st, a);
   hipLaunchKernelGGL(gt_colour_kernel, dim3(CTILES, (unsigned)n), dim3(CT), 0, st, a);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_status();
 }
 
 extern "C" int bbd_error_map(const float* pred, const float* gt, const int32_t* desc, const float* rows,
@@ -201,6 +159,5 @@ extern "C" int bbd_error_map(const float* pred, const float* gt, const int32_t* 
   a.min_depth = (float)min_depth; a.max_depth = (float)max_depth; a.scale_factor = (float)scale_factor;
   a.err_max = (float)err_max;
   hipLaunchKernelGGL(error_map_kernel, dim3(CTILES, (unsigned)n), dim3(CT), 0, static_cast<hipStream_t>(stream), a);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_status();
 }

@@ -16,6 +16,7 @@
 
 #include "../../include/bbd_hip.h"
 #include "bbd_math.h"
+#include "bbd_device_util.h"
 #include "bbd_eval_math.h"
 
 namespace {
@@ -34,22 +35,9 @@ struct EvalArgs {
   int flags;
 };
 
-__device__ __forceinline__ uint32_t order_key(float v) {   // monotone float -> uint
-  const uint32_t b = __float_as_uint(v);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float key_value(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
 // Prediction at ground-truth pixel (y, x) of a GH x GW map (bbd_eval_math.h, shared with bbd_syns.hip).
 __device__ __forceinline__ float resample(const EvalArgs& a, const float* img, int y, int x, int GH, int GW) {
   return bbd_eval_resample(img, a.h, a.w, a.scale_factor, a.clamp_lo, a.clamp_hi, a.flags, y, x, GH, GW);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
 }
 
 __global__ __launch_bounds__(ET) void depth_metrics_kernel(EvalArgs a) {
@@ -58,10 +46,9 @@ __global__ __launch_bounds__(ET) void depth_metrics_kernel(EvalArgs a) {
   __shared__ double red[EW][8];
 
   const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int32_t* d = a.desc + (size_t)img * BBD_EVAL_DESC;
-  const size_t off = (size_t)(uint32_t)d[0] | ((size_t)(uint32_t)d[1] << 32);
-  const int GH = d[2], GW = d[3], r0 = d[4], r1 = d[5], c0 = d[6], c1 = d[7];
-  const float* gt = a.gt + off;
+  const BbdEvalRow m = bbd_eval_row(a.desc, img);
+  const int GH = m.GH, GW = m.GW, r0 = m.r0, r1 = m.r1, c0 = m.c0, c1 = m.c1;
+  const float* gt = a.gt + m.off;
   const float* pr = a.pred + (size_t)img * a.h * a.w;
   float* out = a.out + (size_t)img * BBD_EVAL_OUT;
   const int ww = c1 - c0, npx = (r1 - r0) * ww;
@@ -80,7 +67,7 @@ __global__ __launch_bounds__(ET) void depth_metrics_kernel(EvalArgs a) {
       const int y = r0 + i / ww, x = c0 + i % ww;
       const float g = gt[(size_t)y * GW + x];
       if (!(g > a.min_depth && g < a.max_depth)) continue;
-      const uint32_t kg = order_key(g), kp = order_key(resample(a, pr, y, x, GH, GW));
+      const uint32_t kg = bbd_viz_order_key(g), kp = bbd_viz_order_key(resample(a, pr, y, x, GH, GW));
       if (level == 0) {
         atomicAdd(&hist[0][kg >> 21], 1u);
         atomicAdd(&hist[2][kp >> 21], 1u);
@@ -130,10 +117,10 @@ __global__ __launch_bounds__(ET) void depth_metrics_kernel(EvalArgs a) {
     if (tid < BBD_EVAL_OUT) out[tid] = tid == 10 ? 0.0f : __uint_as_float(0x7fc00000u);
     return;
   }
-  float med_gt = key_value(q_prefix[0]), med_pr = key_value(q_prefix[2]);
+  float med_gt = bbd_viz_key_value(q_prefix[0]), med_pr = bbd_viz_key_value(q_prefix[2]);
   if (a.flags & BBD_EVAL_MEDIAN_MIDPOINT) {      // np.median: mean of the two middle values
-    med_gt = (med_gt + key_value(q_prefix[1])) / 2.0f;
-    med_pr = (med_pr + key_value(q_prefix[3])) / 2.0f;
+    med_gt = (med_gt + bbd_viz_key_value(q_prefix[1])) / 2.0f;
+    med_pr = (med_pr + bbd_viz_key_value(q_prefix[3])) / 2.0f;
   }
   const float ratio = (a.flags & BBD_EVAL_NO_MEDIAN_SCALING) ? 1.0f : med_gt / med_pr;
 
@@ -192,6 +179,5 @@ extern "C" int bbd_depth_metrics(const float* pred, const float* gt, const int32
   a.clamp_lo = (float)clamp_lo; a.clamp_hi = (float)clamp_hi;
   a.scale_factor = (float)scale_factor; a.flags = flags;
   hipLaunchKernelGGL(depth_metrics_kernel, dim3((unsigned)n), dim3(ET), 0, static_cast<hipStream_t>(stream), a);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_status();
 }

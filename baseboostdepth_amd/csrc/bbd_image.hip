@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "../../include/bbd_hip.h"
+#include "bbd_device_util.h"
 #include "bbd_image_math.h"
 
 namespace {
@@ -38,10 +39,6 @@ struct ResampleJob {      // BBD_RESAMPLE_JOB int32 fields
 };
 static_assert(sizeof(ResampleJob) == BBD_RESAMPLE_JOB * 4, "job layout");
 
-__device__ __forceinline__ size_t off64(int32_t lo, int32_t hi) {
-  return (size_t)(uint32_t)lo | ((size_t)(uint32_t)hi << 32);
-}
-
 // out[row][x][c] = clip8(2^21 + sum_j k[x][j] * in[row][xmin + j][c]); flip mirrors the source columns.
 // A workgroup stages RH source rows in LDS with aligned dword loads (rows start at arbitrary byte
 // addresses: 1242*3 is not a multiple of 4), then every thread produces its output columns for all RH
@@ -54,8 +51,8 @@ __global__ __launch_bounds__(NT) void resample_h_kernel(const uint8_t* src, uint
   const ResampleJob jb = jobs[blockIdx.y];
   const int row0 = blockIdx.x * RH;
   if (row0 >= jb.in_h) return;
-  const uint8_t* in = src + off64(jb.src_lo, jb.src_hi);
-  uint8_t* out = dst + off64(jb.dst_lo, jb.dst_hi);
+  const uint8_t* in = src + bbd_join64(jb.src_lo, jb.src_hi);
+  uint8_t* out = dst + bbd_join64(jb.dst_lo, jb.dst_hi);
   const int out_w = jb.out_size, in_w = jb.in_w;
   const int flip = jb.flags & BBD_RESAMPLE_FLIP;
   const int rows = jb.in_h - row0 < RH ? jb.in_h - row0 : RH;
@@ -121,8 +118,8 @@ __global__ __launch_bounds__(NT) void resample_v_kernel(const uint8_t* src, uint
   const int rowbytes = jb.in_w * C;
   const int b = (blockIdx.x * NT + threadIdx.x) * 4;
   if (y0 >= jb.out_size || b >= rowbytes) return;
-  const uint8_t* in = src + off64(jb.src_lo, jb.src_hi);
-  uint8_t* out = dst + off64(jb.dst_lo, jb.dst_hi);
+  const uint8_t* in = src + bbd_join64(jb.src_lo, jb.src_hi);
+  uint8_t* out = dst + bbd_join64(jb.dst_lo, jb.dst_hi);
   const int ys = jb.out_size - y0 < RV ? jb.out_size - y0 : RV;
   const bool words = ((rowbytes & 3) == 0) && (((uintptr_t)in & 3u) == 0) && (((uintptr_t)out & 3u) == 0);
   const int nb = rowbytes - b < 4 ? rowbytes - b : 4;
@@ -185,7 +182,7 @@ __global__ __launch_bounds__(NT) void jitter_sum_kernel(const uint8_t* src, cons
   const JitterJob jb = jobs[blockIdx.y];
   const int cs = contrast_slot(jb);
   if (cs == 4) return;
-  const uint8_t* in = src + off64(jb.src_lo, jb.src_hi);
+  const uint8_t* in = src + bbd_join64(jb.src_lo, jb.src_hi);
   uint32_t local = 0;
   for (int p = blockIdx.x * NT + threadIdx.x; p < npx; p += gridDim.x * NT) {
     uint8_t r = in[3 * (size_t)p], g = in[3 * (size_t)p + 1], b = in[3 * (size_t)p + 2];
@@ -200,8 +197,8 @@ __global__ __launch_bounds__(NT) void jitter_sum_kernel(const uint8_t* src, cons
 __global__ __launch_bounds__(NT) void jitter_apply_kernel(const uint8_t* src, float* dst, const JitterJob* jobs,
                                                           const uint32_t* lsum, int npx) {
   const JitterJob jb = jobs[blockIdx.y];
-  const uint8_t* in = src + off64(jb.src_lo, jb.src_hi);
-  float* out = dst + off64(jb.dst_lo, jb.dst_hi);
+  const uint8_t* in = src + bbd_join64(jb.src_lo, jb.src_hi);
+  float* out = dst + bbd_join64(jb.dst_lo, jb.dst_hi);
   const int cs = contrast_slot(jb);
   const uint8_t mean_l = cs == 4 ? 0 : bbd_img_mean_level(lsum[blockIdx.y], (uint64_t)npx);
   for (int p = blockIdx.x * NT + threadIdx.x; p < npx; p += gridDim.x * NT) {
@@ -215,18 +212,13 @@ __global__ __launch_bounds__(NT) void jitter_apply_kernel(const uint8_t* src, fl
 
 __global__ __launch_bounds__(NT) void to_float_kernel(const uint8_t* src, float* dst, const int32_t* jobs, int npx) {
   const int32_t* jb = jobs + (size_t)blockIdx.y * BBD_CONVERT_JOB;
-  const uint8_t* in = src + off64(jb[0], jb[1]);
-  float* out = dst + off64(jb[2], jb[3]);
+  const uint8_t* in = src + bbd_join64(jb[0], jb[1]);
+  float* out = dst + bbd_join64(jb[2], jb[3]);
   for (int p = blockIdx.x * NT + threadIdx.x; p < npx; p += gridDim.x * NT) {
     out[p] = (float)in[3 * (size_t)p] / 255.0f;
     out[(size_t)npx + p] = (float)in[3 * (size_t)p + 1] / 255.0f;
     out[2 * (size_t)npx + p] = (float)in[3 * (size_t)p + 2] / 255.0f;
   }
-}
-
-int status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
 }
 
 }  // namespace
@@ -242,7 +234,7 @@ int bbd_resample_h_u8(const uint8_t* src, uint8_t* dst, const int32_t* jobs, int
   if (channels == 3) hipLaunchKernelGGL(resample_h_kernel<3>, grid, dim3(NT), 0, st, src, dst, jt, coef, bounds);
   else if (channels == 1) hipLaunchKernelGGL(resample_h_kernel<1>, grid, dim3(NT), 0, st, src, dst, jt, coef, bounds);
   else return BBD_E_BADARG;
-  return status();
+  return launch_status();
 }
 
 int bbd_resample_v_u8(const uint8_t* src, uint8_t* dst, const int32_t* jobs, int n_jobs, int max_out_h,
@@ -254,7 +246,7 @@ int bbd_resample_v_u8(const uint8_t* src, uint8_t* dst, const int32_t* jobs, int
                           (unsigned)n_jobs),
                      dim3(NT), 0, static_cast<hipStream_t>(stream), src, dst,
                      reinterpret_cast<const ResampleJob*>(jobs), coef, bounds, channels);
-  return status();
+  return launch_status();
 }
 
 int bbd_color_jitter_u8(const uint8_t* src, float* dst, const int32_t* jobs, int n_jobs, int H, int W,
@@ -269,7 +261,7 @@ int bbd_color_jitter_u8(const uint8_t* src, float* dst, const int32_t* jobs, int
                      reinterpret_cast<const JitterJob*>(jobs), lsum_scratch, npx);
   hipLaunchKernelGGL(jitter_apply_kernel, dim3(gx, (unsigned)n_jobs), dim3(NT), 0, st, src, dst,
                      reinterpret_cast<const JitterJob*>(jobs), lsum_scratch, npx);
-  return status();
+  return launch_status();
 }
 
 int bbd_u8_to_float_chw(const uint8_t* src, float* dst, const int32_t* jobs, int n_jobs, int H, int W, void* stream) {
@@ -277,7 +269,7 @@ int bbd_u8_to_float_chw(const uint8_t* src, float* dst, const int32_t* jobs, int
   const int npx = H * W;
   hipLaunchKernelGGL(to_float_kernel, dim3((unsigned)((npx + NT * 4 - 1) / (NT * 4)), (unsigned)n_jobs), dim3(NT), 0,
                      static_cast<hipStream_t>(stream), src, dst, jobs, npx);
-  return status();
+  return launch_status();
 }
 
 }  // extern "C"

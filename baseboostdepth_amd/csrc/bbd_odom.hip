@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "../../include/bbd_hip.h"
+#include "bbd_device_util.h"
 #include "bbd_odom_math.h"
 
 namespace {
@@ -75,11 +76,6 @@ __global__ __launch_bounds__(NT) void odom_summary_kernel(const double* __restri
     summary[row * 4 + 2] = (double)tracks;
     summary[row * 4 + 3] = 0.0;
   }
-}
-
-int launch_status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
 }
 
 }  // namespace

@@ -20,12 +20,12 @@
 #include "bbd_math.h"
 #include "bbd_viz_math.h"
 #include "bbd_panel_math.h"
+#include "bbd_device_util.h"
 
 namespace {
 
 constexpr int PT = 256;              // threads per workgroup
-constexpr int PW = PT / 64;          // waves
-constexpr int PARTS = 16;            // partial extrema per SCALAR tile
+constexpr int PARTS = BBD_EXTREMA_PARTS;   // partial extrema per SCALAR tile
 constexpr int MAX_GX = 1024;         // workgroups per cell at most (grid-stride beyond)
 
 struct PanelArgs {
@@ -46,7 +46,7 @@ struct Tile {
 };
 
 __device__ __forceinline__ const void* address(int32_t lo, int32_t hi) {
-  return reinterpret_cast<const void*>((uintptr_t)(uint32_t)lo | ((uintptr_t)(uint32_t)hi << 32));
+  return reinterpret_cast<const void*>(bbd_join64(lo, hi));
 }
 
 __device__ __forceinline__ Tile load_tile(const PanelArgs& a, int t) {
@@ -60,26 +60,12 @@ __device__ __forceinline__ Tile load_tile(const PanelArgs& a, int t) {
 }
 
 __global__ __launch_bounds__(PT) void panel_extrema_kernel(PanelArgs a) {
-  __shared__ uint32_t sh[2 * PW];
-  const int t = blockIdx.y, part = blockIdx.x, tid = threadIdx.x;
+  const int t = blockIdx.y;
   const Tile tl = load_tile(a, t);
   if (tl.kind != BBD_PANEL_SCALAR || tl.src == nullptr) return;            // uniform
   const float* plane = static_cast<const float*>(tl.src);
-  const uint32_t npx = (uint32_t)a.dm.H * (uint32_t)a.dm.W;
-  uint32_t inv_min = 0u, max_key = 0u;
-  for (uint32_t i = (uint32_t)part * PT + tid; i < npx; i += (uint32_t)PARTS * PT)
-    bbd_panel_minmax_update(plane[i], &inv_min, &max_key);
-  for (int o = 32; o > 0; o >>= 1) {
-    inv_min = max(inv_min, (uint32_t)__shfl_down(inv_min, o, 64));
-    max_key = max(max_key, (uint32_t)__shfl_down(max_key, o, 64));
-  }
-  if ((tid & 63) == 0) { sh[2 * (tid >> 6)] = inv_min; sh[2 * (tid >> 6) + 1] = max_key; }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < PW; ++w) { inv_min = max(inv_min, sh[2 * w]); max_key = max(max_key, sh[2 * w + 1]); }
-    uint32_t* sc = a.scratch + ((size_t)t * PARTS + part) * 2;
-    sc[0] = inv_min; sc[1] = max_key;
-  }
+  extrema_part<PT>((uint32_t)a.dm.H * (uint32_t)a.dm.W, [&](uint32_t i) { return plane[i]; },
+                   a.scratch + ((size_t)t * PARTS + blockIdx.x) * 2);
 }
 
 __global__ __launch_bounds__(PT) void panel_render_kernel(PanelArgs a) {
@@ -97,16 +83,9 @@ __global__ __launch_bounds__(PT) void panel_render_kernel(PanelArgs a) {
 
   float vmin = 0.0f, vmax = 0.0f;
   float pj[21];
-  if (kind == BBD_PANEL_SCALAR || kind == BBD_PANEL_ARGMIN) {      // uniform
-    for (int i = tid; i < BBD_PANEL_LUT_ROWS; i += PT)
-      lut[i] = (uint32_t)a.lut[3 * i] | ((uint32_t)a.lut[3 * i + 1] << 8) | ((uint32_t)a.lut[3 * i + 2] << 16);
-    __syncthreads();
-  }
+  if (kind == BBD_PANEL_SCALAR || kind == BBD_PANEL_ARGMIN) stage_lut<BBD_PANEL_LUT_ROWS, PT>(lut, a.lut);   // uniform
   if (kind == BBD_PANEL_SCALAR) {
-    const uint32_t* sc = a.scratch + (size_t)t * PARTS * 2;
-    uint32_t inv_min = 0u, max_key = 0u;
-    for (int p = 0; p < PARTS; ++p) { inv_min = max(inv_min, sc[2 * p]); max_key = max(max_key, sc[2 * p + 1]); }
-    bbd_panel_minmax_values(inv_min, max_key, &vmin, &vmax);
+    extrema_combine(a.scratch + (size_t)t * PARTS * 2, &vmin, &vmax);
     if (blockIdx.x == 0 && tid == 0) { a.stats[(size_t)t * 2] = vmin; a.stats[(size_t)t * 2 + 1] = vmax; }
   }
   if (kind == BBD_PANEL_WARP) bbd_make_proj(a.pose + (size_t)tl.p0 * BBD_POSE_STRIDE, pj);
@@ -136,16 +115,7 @@ __global__ __launch_bounds__(PT) void panel_render_kernel(PanelArgs a) {
       }
     }
     uint8_t* o = a.out + (((size_t)row * H + y) * out_row + (size_t)col * W + x0) * 3;
-    if (cnt == 4 && (((uintptr_t)o) & 3u) == 0) {                  // 12 bytes per lane, contiguous across the wave
-      uint32_t* o32 = reinterpret_cast<uint32_t*>(o);
-      o32[0] = c[0] | (c[1] << 24);
-      o32[1] = (c[1] >> 8) | (c[2] << 16);
-      o32[2] = (c[2] >> 16) | (c[3] << 8);
-    } else {
-      for (int k = 0; k < cnt; ++k) {
-        o[3 * k] = (uint8_t)c[k]; o[3 * k + 1] = (uint8_t)(c[k] >> 8); o[3 * k + 2] = (uint8_t)(c[k] >> 16);
-      }
-    }
+    store_quad(o, (((uintptr_t)o) & 3u) == 0, (uint32_t)cnt, c);
   }
 }
 
@@ -207,8 +177,7 @@ extern "C" int bbd_train_panel(const int32_t* desc, const float* pose, const uin
   const unsigned gx = (ngroups + PT - 1) / PT;
   hipLaunchKernelGGL(panel_render_kernel, dim3(gx < (unsigned)MAX_GX ? gx : (unsigned)MAX_GX, (unsigned)(rows * cols)), dim3(PT),
                      0, st, a);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_status();
 }
 
 extern "C" int bbd_argmin_hist(const uint8_t* argmin, int32_t* counts, int B, int n_px, void* stream) {
@@ -220,6 +189,5 @@ extern "C" int bbd_argmin_hist(const uint8_t* argmin, int32_t* counts, int B, in
   unsigned gx = ((unsigned)n_px + per - 1) / per;
   gx = gx < 1u ? 1u : (gx > 256u ? 256u : gx);
   hipLaunchKernelGGL(argmin_hist_kernel, dim3(gx, (unsigned)B), dim3(PT), 0, st, argmin, counts, (uint32_t)n_px);
-  e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_status();
 }

@@ -13,6 +13,7 @@
 #include <stddef.h>
 
 #include "../../include/bbd_hip.h"
+#include "bbd_device_util.h"
 #include "bbd_postproc_math.h"
 
 namespace {
@@ -45,6 +46,5 @@ extern "C" int bbd_post_process_disp(const float* disp, float* out, int n, int h
   const unsigned gy = (unsigned)(rows < want_y ? rows : want_y);
   hipLaunchKernelGGL(post_process_kernel, dim3(gx, gy), dim3(PT), 0, static_cast<hipStream_t>(stream), disp, out, rows,
                      w, bbd_postproc_step(w));
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_status();
 }

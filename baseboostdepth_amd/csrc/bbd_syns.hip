@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "../../include/bbd_hip.h"
+#include "bbd_device_util.h"
 #include "bbd_eval_math.h"
 #include "bbd_syns_math.h"
 
@@ -48,11 +49,11 @@ struct Img {
 };
 
 __device__ __forceinline__ Img load_img(const int32_t* desc, int i, int px_stride) {
-  const int32_t* d = desc + (size_t)i * BBD_EVAL_DESC;
+  const BbdEvalRow row = bbd_eval_row(desc, i);
   Img m;
-  m.off = (size_t)(uint32_t)d[0] | ((size_t)(uint32_t)d[1] << 32);
-  m.GH = d[2];
-  m.GW = d[3];
+  m.off = row.off;
+  m.GH = row.GH;
+  m.GW = row.GW;
   m.ok = m.GH >= 1 && m.GW >= 1 && (long)m.GH * (long)m.GW <= (long)px_stride;   // a row that does not fit is skipped
   m.npx = m.ok ? m.GH * m.GW : 0;
   return m;
@@ -69,27 +70,6 @@ struct PredArgs {
 __device__ __forceinline__ float pred_at(const PredArgs& a, int img, int y, int x, int GH, int GW) {
   return bbd_eval_resample(a.pred + (size_t)img * a.h * a.w, a.h, a.w, a.scale_factor, a.clamp_lo, a.clamp_hi,
                            a.flags & BBD_EVAL_PRED_IS_DISP, y, x, GH, GW);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-
-// Sum of one value per thread over a workgroup of RT threads, in a fixed order; valid in every thread afterwards.
-__device__ __forceinline__ double block_sum(double v, double* red /* [RW + 1] shared */) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const double r = wave_sum(v);
-  __syncthreads();
-  if (lane == 0) red[wave] = r;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0;
-    for (int wv = 0; wv < RW; ++wv) s += red[wv];
-    red[RW] = s;
-  }
-  __syncthreads();
-  return red[RW];
 }
 
 // ------------------------------------------------------------------------------------------------ edges
@@ -133,7 +113,7 @@ __global__ __launch_bounds__(RT) void syns_thresh_kernel(const int32_t* desc, in
   if (tid == 0) s_count = 0u;
   double s = 0;
   for (int p = tid; p < m.npx; p += RT) s += in[p];
-  const double mean = block_sum(s, red) / (double)m.npx;    // an empty image: 0 / 0, as np.mean of nothing
+  const double mean = block_sum<RT>(s, red) / (double)m.npx;    // an empty image: 0 / 0, as np.mean of nothing
   unsigned int c = 0;
   for (int p = tid; p < m.npx; p += RT) {
     const uint8_t e = in[p] > mean ? 1 : 0;
@@ -262,9 +242,9 @@ __global__ __launch_bounds__(RT) void syns_edge_reduce_kernel(ReduceArgs a) {
       n_valid += 1u;
     }
   }
-  s_acc = block_sum(s_acc, red);
-  s_comp = block_sum(s_comp, red);
-  s_err = block_sum(s_err, red);
+  s_acc = block_sum<RT>(s_acc, red);
+  s_comp = block_sum<RT>(s_comp, red);
+  s_err = block_sum<RT>(s_err, red);
   atomicAdd(&cnt[0], n_near);
   atomicAdd(&cnt[1], n_tgt);
   atomicAdd(&cnt[2], n_valid);
@@ -461,11 +441,6 @@ void launch_edt(const EdtArgs& a, int n, int max_h, int max_w, hipStream_t st) {
   hipLaunchKernelGGL(syns_edt_row_kernel, dim3((unsigned)max_h, (unsigned)n), dim3(PT), 0, st, a);
 }
 
-int last_status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
-}
-
 PredArgs pred_args(const float* pred, const int32_t* desc, int h, int w, int px_stride, double clamp_lo,
                    double clamp_hi, double scale_factor, int flags) {
   PredArgs p;
@@ -501,7 +476,7 @@ extern "C" int bbd_syns_pred_edges(const float* pred, const int32_t* desc, int32
   hipLaunchKernelGGL(syns_sobel_kernel, grid, dim3(PT), 0, st, desc, px_stride, (const float*)B, mag);
   hipLaunchKernelGGL(syns_thresh_kernel, dim3((unsigned)n), dim3(RT), 0, st, desc, px_stride, (const double*)mag, edge,
                      stats);
-  return last_status();
+  return launch_status();
 }
 
 extern "C" int bbd_syns_edt(const uint8_t* map, const int32_t* desc, int32_t* out, int n, int px_stride, int max_h,
@@ -513,7 +488,7 @@ extern "C" int bbd_syns_edt(const uint8_t* map, const int32_t* desc, int32_t* ou
   a.map = map; a.gt = nullptr; a.gt_edge = nullptr; a.desc = desc; a.out = out; a.mask_out = nullptr;
   a.px_stride = px_stride; a.lo = 0.0f; a.hi = 0.0f;
   launch_edt(a, n, max_h, max_w, static_cast<hipStream_t>(stream));
-  return last_status();
+  return launch_status();
 }
 
 extern "C" int bbd_syns_edge_metrics(const float* pred, const float* gt, const uint8_t* gt_edge,
@@ -543,7 +518,7 @@ extern "C" int bbd_syns_edge_metrics(const float* pred, const float* gt, const u
   r.gt = gt; r.rows = rows; r.pred_edge = pred_edge; r.tgt = tgt; r.d_t = d_t; r.d_p = d_p; r.out = out;
   r.lo = (float)min_depth; r.hi = (float)max_depth; r.th = th;
   hipLaunchKernelGGL(syns_edge_reduce_kernel, dim3((unsigned)n), dim3(RT), 0, st, r);
-  return last_status();
+  return launch_status();
 }
 
 extern "C" int bbd_chamfer_nn(const float* a, const float* b, int na, int nb, float* nn_a, float* nn_b, void* stream) {
@@ -560,7 +535,7 @@ extern "C" int bbd_chamfer_nn(const float* a, const float* b, int na, int nb, fl
   hipLaunchKernelGGL(syns_nn_kernel, dim3((unsigned)((na + NN_T * NN_Q - 1) / (NN_T * NN_Q)), NN_SPLIT, 1), dim3(NN_T), 0, st, q);
   q.q = b; q.t = a; q.nq = nb; q.nt = na; q.out = reinterpret_cast<uint32_t*>(nn_b);
   hipLaunchKernelGGL(syns_nn_kernel, dim3((unsigned)((nb + NN_T * NN_Q - 1) / (NN_T * NN_Q)), NN_SPLIT, 1), dim3(NN_T), 0, st, q);
-  return last_status();
+  return launch_status();
 }
 
 extern "C" int bbd_syns_pointcloud(const float* pred, const float* gt, const int32_t* desc, const float* rows,
@@ -600,5 +575,5 @@ extern "C" int bbd_syns_pointcloud(const float* pred, const float* gt, const int
   CloudReduceArgs r;
   r.nn_p = nn_p; r.nn_t = nn_t; r.counts = counts; r.out = out; r.px_stride = px_stride; r.th = (float)th;
   hipLaunchKernelGGL(syns_cloud_reduce_kernel, dim3((unsigned)n), dim3(RT), 0, st, r);
-  return last_status();
+  return launch_status();
 }

@@ -28,6 +28,7 @@
 
 #include "../../include/bbd_hip.h"
 #include "bbd_velo_math.h"
+#include "bbd_device_util.h"
 
 namespace {
 
@@ -57,7 +58,7 @@ struct Frame {
 __device__ __forceinline__ Frame load_frame(const VeloArgs& a, int f) {
   const int32_t* d = a.desc + (size_t)f * BBD_VELO_DESC;
   Frame fr;
-  fr.off = (size_t)(uint32_t)d[0] | ((size_t)(uint32_t)d[1] << 32);
+  fr.off = bbd_join64(d[0], d[1]);
   fr.h = d[2];
   fr.w = d[3];
   fr.n_points = d[4];
@@ -132,6 +133,5 @@ extern "C" int bbd_velo_depth(const float* points, const int32_t* desc, const do
   if (max_points > 0)
     hipLaunchKernelGGL(velo_point_kernel, dim3((unsigned)((max_points + VT - 1) / VT), (unsigned)n_frames), dim3(VT), 0, st, a);
   hipLaunchKernelGGL(velo_pixel_kernel, dim3(VTILES, (unsigned)n_frames), dim3(VT), 0, st, a);
-  e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_status();
 }

@@ -21,6 +21,7 @@
 #include "../../include/bbd_hip.h"
 #include "bbd_math.h"
 #include "bbd_viz_math.h"
+#include "bbd_device_util.h"
 
 namespace {
 
@@ -53,7 +54,7 @@ struct Image {
 __device__ __forceinline__ Image load_image(const VizArgs& a, int img) {
   const int32_t* d = a.desc + (size_t)img * BBD_VIZ_DESC;
   Image im;
-  im.off = (size_t)(uint32_t)d[0] | ((size_t)(uint32_t)d[1] << 32);
+  im.off = bbd_join64(d[0], d[1]);
   im.H0 = d[2];
   im.W0 = d[3];
   im.npx = (uint32_t)im.H0 * (uint32_t)im.W0;
@@ -171,7 +172,7 @@ __global__ __launch_bounds__(VT) void viz_hist_kernel(VizArgs a) {
     if (c) atomicAdd(g + i, c);
   }
   if (LEVEL == 0) {
-    for (int o = 32; o > 0; o >>= 1) inv_min = max(inv_min, (uint32_t)__shfl_down(inv_min, o, 64));
+    inv_min = wave_max(inv_min);
     if ((tid & 63) == 0) atomicMax(sc + SC_MIN, inv_min);
   }
 }
@@ -191,8 +192,7 @@ __global__ __launch_bounds__(VT) void viz_colour_kernel(VizArgs a) {
   const uint32_t* sc = a.scratch + (size_t)img * SC_STRIDE;
   const uint32_t nquad = (im.npx + 3u) / 4u;
   if ((uint64_t)tile * VT >= nquad) return;
-  for (int i = tid; i < 256; i += VT)
-    lut[i] = (uint32_t)a.lut[3 * i] | ((uint32_t)a.lut[3 * i + 1] << 8) | ((uint32_t)a.lut[3 * i + 2] << 16);
+  fill_lut<256, VT>(lut, a.lut);                         // published by the barriers of resolve_levels
 
   const Select sel = resolve_levels(a, im, sc, 3, sh);
   const float lower = bbd_viz_key_value(sel.prefix[0]), upper = bbd_viz_key_value(sel.prefix[1]);
@@ -214,17 +214,7 @@ __global__ __launch_bounds__(VT) void viz_colour_kernel(VizArgs a) {
       c[k] = colour_of(a, im, lut, outf, i0 + k, y, x, vmin, vmax);
       if (++x == im.W0) { x = 0; ++y; }
     }
-    if (packed && cnt == 4u) {             // 12 bytes per lane, contiguous across the wave
-      uint32_t* o = reinterpret_cast<uint32_t*>(out + (size_t)i0 * 3);
-      o[0] = c[0] | (c[1] << 24);
-      o[1] = (c[1] >> 8) | (c[2] << 16);
-      o[2] = (c[2] >> 16) | (c[3] << 8);
-    } else {
-      for (uint32_t k = 0; k < cnt; ++k) {
-        uint8_t* o = out + (size_t)(i0 + k) * 3;
-        o[0] = (uint8_t)c[k]; o[1] = (uint8_t)(c[k] >> 8); o[2] = (uint8_t)(c[k] >> 16);
-      }
-    }
+    store_quad(out + (size_t)i0 * 3, packed, cnt, c);
   }
 }
 
@@ -250,6 +240,5 @@ extern "C" int bbd_disp_viz(const float* disp, const int32_t* desc, const uint8_
   hipLaunchKernelGGL(viz_hist_kernel<1>, grid, block, 0, st, a);
   hipLaunchKernelGGL(viz_hist_kernel<2>, grid, block, 0, st, a);
   hipLaunchKernelGGL(viz_colour_kernel, grid, block, 0, st, a);
-  e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_status();
 }

@@ -6,22 +6,39 @@ The .so is git-ignored (history stays source-only) but travels to the GPU box wi
 -ffp-contract=off is REQUIRED: bbd_math.h mirrors the reference CPU path's rounding order and
 places every FMA explicitly.
 """
+import glob
 import os
 import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRCS = [os.path.join(HERE, "bbd_kernels.hip"), os.path.join(HERE, "bbd_eval.hip"),
-        os.path.join(HERE, "bbd_image.hip"), os.path.join(HERE, "bbd_nn.hip"), os.path.join(HERE, "bbd_vit.hip"), os.path.join(HERE, "bbd_pose.hip"), os.path.join(HERE, "bbd_tokens.hip"), os.path.join(HERE, "bbd_util.hip"),
-        os.path.join(HERE, "bbd_viz.hip"), os.path.join(HERE, "bbd_velo.hip"), os.path.join(HERE, "bbd_syns.hip"),
-        os.path.join(HERE, "bbd_odom.hip"), os.path.join(HERE, "bbd_postproc.hip"), os.path.join(HERE, "bbd_panel.hip"),
-        os.path.join(HERE, "bbd_compare.hip")]
+
+
+def _here(names):
+    return [os.path.join(HERE, n) for n in names.split()]
+
+
+SRCS = _here("""
+    bbd_kernels.hip
+    bbd_eval.hip
+    bbd_image.hip
+    bbd_nn.hip
+    bbd_vit.hip
+    bbd_pose.hip
+    bbd_tokens.hip
+    bbd_util.hip
+    bbd_viz.hip
+    bbd_velo.hip
+    bbd_syns.hip
+    bbd_odom.hip
+    bbd_postproc.hip
+    bbd_panel.hip
+    bbd_compare.hip
+""")
 OUT = os.path.join(HERE, "libbbd_hip.so")
-DEPS = SRCS + [os.path.abspath(__file__), os.path.join(HERE, "bbd_math.h"), os.path.join(HERE, "bbd_image_math.h"), os.path.join(HERE, "bbd_viz_math.h"),
-               os.path.join(HERE, "bbd_velo_math.h"), os.path.join(HERE, "bbd_eval_math.h"), os.path.join(HERE, "bbd_syns_math.h"),
-               os.path.join(HERE, "bbd_odom_math.h"), os.path.join(HERE, "bbd_postproc_math.h"),
-               os.path.join(HERE, "bbd_panel_math.h"), os.path.join(HERE, "bbd_compare_math.h"),
-               os.path.join(HERE, "..", "..", "include", "bbd_hip.h")]
+# every header of this directory: one that is forgotten here would leave a stale library behind an edit
+DEPS = SRCS + [os.path.abspath(__file__)] + sorted(glob.glob(os.path.join(HERE, "*.h"))) + [
+    os.path.join(HERE, "..", "..", "include", "bbd_hip.h")]
 # -fno-slp-vectorize: hipcc otherwise SLP-packs neighbouring scalar fp32 adds / multiplies into v_pk_add/mul_f32 and
 # pays for it in v_mov register shuffles (129 moves in the forward's SSIM phase): measured forward 0.222 -> 0.208 ms,
 # identity 0.0365 -> 0.0340 ms, backward 0.348 -> 0.343 ms (profiles/r02/slp_variants.txt).  Same operations, same bits.

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .tables import split64, upload
 from ._lib import (EVAL_DESC, EVAL_OUT, EVAL_PRED_IS_DISP, EVAL_MEDIAN_MIDPOINT, EVAL_NO_MEDIAN_SCALING, SYNS_OUT,
                    SYNS_CLOUD_OUT, SYNS_RAYS_PIXEL, BbdError, ptr)
 
@@ -54,7 +55,7 @@ class GroundTruthSet:
         for i, m in enumerate(maps):
             gh, gw = m.shape
             win = garg_window(gh, gw) if crop else (0, gh, 0, gw)
-            desc[i] = (off & 0xFFFFFFFF if off < 2 ** 31 else (off & 0xFFFFFFFF) - 2 ** 32, off >> 32, gh, gw) + win
+            desc[i] = split64(off) + (gh, gw) + win
             off += m.size
         flat = np.concatenate([m.ravel() for m in maps]) if maps else np.zeros(0, np.float32)
         self.shapes = [m.shape for m in maps]
@@ -74,7 +75,7 @@ class GroundTruthSet:
         off = 0
         for i, (gh, gw) in enumerate(shapes):
             win = garg_window(gh, gw) if crop else (0, gh, 0, gw)
-            desc[i] = (off & 0xFFFFFFFF if off < 2 ** 31 else (off & 0xFFFFFFFF) - 2 ** 32, off >> 32, gh, gw) + win
+            desc[i] = split64(off) + (gh, gw) + win
             off += gh * gw
         self = cls.__new__(cls)
         self.edges = None
@@ -563,7 +564,7 @@ def pose_ate(poses, gt_global, skip=2, track_length=1, backend=None):
         raise ValueError("pose_ate: %d windows of skip %d need %d ground-truth poses, the sequence has %d (N = %d > "
                          "M - S = %d)" % (N, S, N + S, M, N, M - S))
     if gt.device != dev:
-        gt = (gt.pin_memory() if dev.type == "cuda" else gt).to(dev, non_blocking=True)
+        gt = upload(gt, dev)
     gt = gt.contiguous()
     backend._check(poses, gt)
     tracks = max(N - S, 0)
@@ -669,7 +670,7 @@ def evaluate_pose(opt, dataloader=None, gt_poses=None, models=None, batch_window
         first += color.shape[0]
     assert first == F, "the windows need %d frames, the dataloader gave %d" % (F, first)
     # [2, 1+S, N]: first and second frame of every pair, each plane contiguous
-    table = torch.from_numpy(np.ascontiguousarray(pairs.transpose(2, 0, 1))).pin_memory().to(device, non_blocking=True)
+    table = upload(pairs.transpose(2, 0, 1), device)
     poses = torch.empty(1 + S, N, 16, device=device)
     with torch.no_grad():
         for lo in range(0, N, max(1, int(batch_windows))):

@@ -18,6 +18,7 @@ import torch
 
 from . import ops
 from ._lib import RESAMPLE_JOB, RESAMPLE_FLIP, JITTER_JOB, CONVERT_JOB, ptr
+from .tables import split64 as _split64, upload as _upload
 
 PRECISION_BITS = 22
 BRIGHTNESS, CONTRAST, SATURATION, HUE = 0, 1, 2, 3
@@ -66,11 +67,6 @@ def resample_table(in_size, out_size):
     return coef, bounds, ksize
 
 
-def _split64(v):
-    lo = v & 0xFFFFFFFF
-    return (lo - (1 << 32) if lo >= (1 << 31) else lo), v >> 32
-
-
 def float_bits(f):
     return struct.unpack("<i", struct.pack("<f", float(f)))[0]
 
@@ -105,17 +101,6 @@ class TableBank:
         if self.device_tensors is None:
             self.device_tensors = (_upload(np.concatenate(self.coef), device), _upload(np.concatenate(self.bounds), device))
         return self.device_tensors
-
-
-def _upload(array, device):
-    """Host array -> device tensor without blocking the calling thread on the stream (pinned staging + asynchronous copy;
-    the caching host allocator keeps the staging block until the copy has run).  The loader's producer thread plans and
-    launches batches ahead of the training step: a pageable copy would make it wait for its stream - which shares the GPU
-    with a replaying step graph - three times per batch."""
-    t = torch.from_numpy(np.ascontiguousarray(array))
-    if torch.device(device).type != "cuda":
-        return t
-    return t.pin_memory().to(device, non_blocking=True)
 
 
 class _Slot:

@@ -14,6 +14,7 @@ import torch
 from . import _lib
 from ._lib import COMPOSE_STRIDE, COMPOSE_ERROR, COMPOSE_REPLACE, POSE_STRIDE, PROJ_STRIDE, MAX_FRAME_SLOTS, ptr
 from .plan import frame_slot
+from .tables import join64, split64, upload
 
 
 # BBD_FUSED_NN=0 sends the encoder / decoder glue (pad, max-pool) back to the stock ATen kernels (A/B runs)
@@ -1495,17 +1496,21 @@ def dispconv(x, weight, bias, backend=None):
 _MAGMA = {}
 
 
+def _hex_lut(name, n_rows):
+    """uint8 [n_rows,3] from a shipped table of one `rrggbb` row per line."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), name)) as f:
+        rows = [line.strip() for line in f if line.strip()]
+    assert len(rows) == n_rows and all(len(r) == 6 for r in rows)
+    return torch.tensor([[int(r[0:2], 16), int(r[2:4], 16), int(r[4:6], 16)] for r in rows], dtype=torch.uint8)
+
+
 def magma_lut(device="cpu"):
     """uint8 [256,3]: magma as matplotlib's `to_rgba(...)[..., :3] * 255 -> uint8` yields it.  Read from the shipped
     table (magma_lut.hex, written by tools/make_magma_lut.py); matplotlib is never imported."""
     key = str(device)
     if key not in _MAGMA:
         if "cpu" not in _MAGMA:
-            with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "magma_lut.hex")) as f:
-                rows = [line.strip() for line in f if line.strip()]
-            assert len(rows) == 256 and all(len(r) == 6 for r in rows)
-            _MAGMA["cpu"] = torch.tensor([[int(r[0:2], 16), int(r[2:4], 16), int(r[4:6], 16)] for r in rows],
-                                         dtype=torch.uint8)
+            _MAGMA["cpu"] = _hex_lut("magma_lut.hex", 256)
         _MAGMA[key] = _MAGMA["cpu"].to(device)
     return _MAGMA[key]
 
@@ -1545,11 +1550,9 @@ def disp_viz(disp, sizes, min_depth=0.1, max_depth=80.0, percentile=95.0, want_f
     rows, off = [], 0
     for H0, W0 in sizes:
         assert H0 >= 1 and W0 >= 1 and H0 * W0 < 2 ** 31
-        rows.append((off & 0x7FFFFFFF | (-(off >> 31 & 1) << 31), off >> 32, int(H0), int(W0)))
+        rows.append(split64(off) + (int(H0), int(W0)))
         off += viz_granule(H0 * W0)
-    desc = torch.tensor(rows, dtype=torch.int32)
-    if dev.type == "cuda":
-        desc = desc.pin_memory().to(dev, non_blocking=True)
+    desc = upload(torch.tensor(rows, dtype=torch.int32), dev)
     out = torch.empty(off * 3, dtype=torch.uint8, device=dev)
     outf = torch.empty(off, dtype=torch.float32, device=dev) if want_float else None
     stats = torch.empty(n, 4, dtype=torch.float32, device=dev)
@@ -1558,7 +1561,7 @@ def disp_viz(disp, sizes, min_depth=0.1, max_depth=80.0, percentile=95.0, want_f
                 ptr(scratch), n, h, w, *((0.0, 1.0, 100.0) if raw else (1.0 / max_depth, 1.0 / min_depth, float(percentile))))
     colour, floats = [], ([] if want_float else None)
     for (lo, hi, H0, W0) in rows:
-        o = (lo & 0xFFFFFFFF) | (hi << 32)
+        o = join64(lo, hi)
         colour.append(out[3 * o:3 * (o + H0 * W0)].view(H0, W0, 3))
         if want_float:
             floats.append(outf[o:o + H0 * W0].view(H0, W0))
@@ -1575,18 +1578,15 @@ class _GtBatch:
         self.idx = [int(i) for i in indices]
         assert self.idx and all(0 <= i < len(gts) for i in self.idx)
         host = gts.desc_host[self.idx].astype("int64")
-        offs = (host[:, 0] & 0xFFFFFFFF) | (host[:, 1] << 32)
+        offs = join64(host[:, 0], host[:, 1])
         self.shapes = [tuple(int(v) for v in gts.shapes[i]) for i in self.idx]
         sizes = [gh * gw for gh, gw in self.shapes]
         self.base = int(offs.min())
         self.rel = [int(o) - self.base for o in offs]
         self.span = max(r + s for r, s in zip(self.rel, sizes))
         rows = host.copy()
-        rows[:, 0] = [r & 0x7FFFFFFF | (-(r >> 31 & 1) << 31) for r in self.rel]
-        rows[:, 1] = [r >> 32 for r in self.rel]
-        desc = torch.from_numpy(rows.astype("int32"))
-        dev = gts.buffer.device
-        self.desc = desc.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else desc
+        rows[:, :2] = [split64(r) for r in self.rel]
+        self.desc = upload(rows.astype("int32"), gts.buffer.device)
         self.gt = gts.buffer[self.base:]
 
     def pictures(self, buf):
@@ -1683,17 +1683,15 @@ def velo_depth(points, counts, proj, shapes, out=None, offsets=None, vel_depth=F
     backend._check(points, out)
     rows, first_point, first_pixel = [], 0, 0
     for (h, w), c, o, s in zip(shapes, counts, offsets, sizes):
-        rows.append((o & 0x7FFFFFFF | (-(o >> 31 & 1) << 31), o >> 32, int(h), int(w), int(c), first_point, first_pixel, 0))
+        rows.append(split64(int(o)) + (int(h), int(w), int(c), first_point, first_pixel, 0))
         first_point += int(c)
         first_pixel += s
     n_ints = backend.lib.velo_depth_scratch_ints(first_pixel, n)
     if n_ints < 0:
         raise _lib.BbdError("velo_depth: %d pixels in one call are more than the scratch contract holds; "
                             "split the batch" % first_pixel)
-    desc = torch.tensor(rows, dtype=torch.int32)
-    if dev.type == "cuda":
-        desc = desc.pin_memory().to(dev, non_blocking=True)
-        proj = proj.pin_memory().to(dev, non_blocking=True)
+    desc = upload(torch.tensor(rows, dtype=torch.int32), dev)
+    proj = upload(proj, dev)
     scratch = torch.empty(n_ints, dtype=torch.int32, device=dev)
     backend.run("bbd_velo_depth", out, ptr(points), ptr(desc), ptr(proj), ptr(scratch), n_ints, ptr(out), n,
                 int(max(counts)), _lib.VELO_VEL_DEPTH if vel_depth else 0)
@@ -1754,10 +1752,7 @@ def panel_luts(device="cpu"):
     key = str(device)
     if key not in _PANEL_LUTS:
         if "cpu" not in _PANEL_LUTS:
-            with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "panel_luts.hex")) as f:
-                rows = [line.strip() for line in f if line.strip()]
-            assert len(rows) == 276 and all(len(r) == 6 for r in rows)
-            own = torch.tensor([[int(r[0:2], 16), int(r[2:4], 16), int(r[4:6], 16)] for r in rows], dtype=torch.uint8)
+            own = _hex_lut("panel_luts.hex", 276)
             _PANEL_LUTS["cpu"] = torch.cat([own[:256], magma_lut("cpu"), own[256:]], 0).contiguous()
             assert _PANEL_LUTS["cpu"].shape[0] == _lib.PANEL_LUT_ROWS
         _PANEL_LUTS[key] = _PANEL_LUTS["cpu"].to(device)
@@ -1765,9 +1760,7 @@ def panel_luts(device="cpu"):
 
 
 def _addr_words(t):
-    a = 0 if t is None else t.data_ptr()
-    lo, hi = a & 0xFFFFFFFF, (a >> 32) & 0xFFFFFFFF
-    return lo - (1 << 32) if lo >= 1 << 31 else lo, hi - (1 << 32) if hi >= 1 << 31 else hi
+    return split64(0 if t is None else t.data_ptr())
 
 
 def train_panel(tiles, pose_table, H, W, rows, cols, backend=None):
@@ -1817,9 +1810,7 @@ def train_panel(tiles, pose_table, H, W, rows, cols, backend=None):
         desc.append((kinds[kind], r * cols + c) + _addr_words(src) + _addr_words(aux) + (p0, p1))
     backend._check(pose_table)
     n = len(desc)
-    desc = torch.tensor(desc, dtype=torch.int32)
-    if dev.type == "cuda":
-        desc = desc.pin_memory().to(dev, non_blocking=True)
+    desc = upload(torch.tensor(desc, dtype=torch.int32), dev)
     out = torch.empty(rows * H, cols * W, 3, dtype=torch.uint8, device=dev)
     stats = torch.zeros(n, 2, dtype=torch.float32, device=dev)
     scratch = torch.empty(backend.lib.train_panel_scratch_ints(n), dtype=torch.int32, device=dev)

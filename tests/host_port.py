@@ -5,24 +5,12 @@ baseboostdepth_amd.ops so the CPU tier exercises the product's Python plumbing (
 projection table, autograd wrappers) together with the exact per-pixel math of the HIP kernels.
 """
 import ctypes
-import os
-import subprocess
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "host_port", "bbd_host_port.cpp")
-SRC_IMAGE = os.path.join(HERE, "host_port", "bbd_image_port.cpp")
-LIB = os.path.join(HERE, "host_port", "libbbd_host_port.so")
-DEPS = [SRC, SRC_IMAGE, os.path.join(HERE, "..", "baseboostdepth_amd", "csrc", "bbd_math.h"),
-        os.path.join(HERE, "..", "baseboostdepth_amd", "csrc", "bbd_image_math.h"),
-        os.path.join(HERE, "..", "include", "bbd_hip.h")]
+from port_build import build_port, call_port
 
 
 def build():
-    if os.path.isfile(LIB) and all(os.path.getmtime(LIB) >= os.path.getmtime(d) for d in DEPS):
-        return LIB
-    cmd = ["g++", "-O2", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-std=c++17", "-o", LIB, SRC, SRC_IMAGE]
-    subprocess.run(cmd, check=True)
-    return LIB
+    return build_port("libbbd_host_port.so", ["bbd_host_port.cpp", "bbd_image_port.cpp"])
 
 
 class HostPortBackend:
@@ -52,17 +40,7 @@ class HostPortBackend:
             assert t is None or not t.is_cuda
 
     def run(self, name, anchor, *args):
-        fn = getattr(self.dll, name.replace("bbd_", "hp_"))
-        fn.restype = ctypes.c_int
-        conv = []
-        for a in args:
-            if isinstance(a, float):
-                conv.append(ctypes.c_double(a))
-            elif isinstance(a, int):
-                conv.append(ctypes.c_int(a))
-            else:
-                conv.append(a)
-        rc = fn(*conv)
+        rc = call_port(self.dll, name, args)
         assert rc == 0, (name, rc)
 
     def check_div(self, start, count, stride):

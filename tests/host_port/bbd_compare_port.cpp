@@ -11,29 +11,23 @@
 #include "../../include/bbd_hip.h"
 #include "../../baseboostdepth_amd/csrc/bbd_panel_math.h"
 #include "../../baseboostdepth_amd/csrc/bbd_compare_math.h"
+#include "../../baseboostdepth_amd/csrc/bbd_ragged_math.h"
 
 namespace {
 
-struct Map {
-  size_t off;
-  int GH, GW, r0, r1, c0, c1;
+struct Map : BbdEvalRow {
   size_t npx;
 };
 
 Map load_map(const int32_t* desc, int i) {
-  const int32_t* d = desc + (size_t)i * BBD_EVAL_DESC;
   Map m;
-  m.off = (size_t)(uint32_t)d[0] | ((size_t)(uint32_t)d[1] << 32);
-  m.GH = d[2]; m.GW = d[3]; m.r0 = d[4]; m.r1 = d[5]; m.c0 = d[6]; m.c1 = d[7];
+  static_cast<BbdEvalRow&>(m) = bbd_eval_row(desc, i);
   m.npx = m.GH > 0 && m.GW > 0 ? (size_t)m.GH * (size_t)m.GW : 0;
   return m;
 }
 
-void put(uint8_t* o, uint32_t c) { o[0] = (uint8_t)c; o[1] = (uint8_t)(c >> 8); o[2] = (uint8_t)(c >> 16); }
-
 void pack_lut(uint32_t* packed, const uint8_t* lut) {
-  for (int i = 0; i < 256; ++i)
-    packed[i] = (uint32_t)lut[3 * i] | ((uint32_t)lut[3 * i + 1] << 8) | ((uint32_t)lut[3 * i + 2] << 16);
+  for (int i = 0; i < 256; ++i) packed[i] = bbd_pack_rgb(lut + 3 * i);
 }
 
 }  // namespace
@@ -56,7 +50,7 @@ extern "C" int hp_gt_viz(const float* gt, const int32_t* desc, const uint8_t* lu
     stats[(size_t)img * 2] = vmin;
     stats[(size_t)img * 2 + 1] = vmax;
     for (size_t i = 0; i < m.npx; ++i)
-      put(out_u8 + 3 * (m.off + i), packed[bbd_viz_lut_index(bbd_compare_gt_inverse(g[i], max_inv), vmin, vmax)]);
+      bbd_put_rgb(out_u8 + 3 * (m.off + i), packed[bbd_viz_lut_index(bbd_compare_gt_inverse(g[i], max_inv), vmin, vmax)]);
   }
   return 0;
 }
@@ -92,7 +86,7 @@ extern "C" int hp_error_map(const float* pred, const float* gt, const int32_t* d
         uint32_t c = 0u;
         if (any) c = packed[bbd_viz_lut_index(e, 0.0f, err_max)];
         else if (images) c = bbd_compare_grey(images + 3 * i);
-        put(out_u8 + 3 * i, c);
+        bbd_put_rgb(out_u8 + 3 * i, c);
       }
   }
   return 0;

@@ -7,11 +7,11 @@
 
 #include "../../include/bbd_hip.h"
 #include "../../baseboostdepth_amd/csrc/bbd_image_math.h"
+#include "../../baseboostdepth_amd/csrc/bbd_ragged_math.h"
 
 namespace {
 struct RJob { int32_t src_lo, src_hi, dst_lo, dst_hi, in_h, in_w, out_size, ksize, coef_off, bounds_off, flags, pad; };
 struct JJob { int32_t src_lo, src_hi, dst_lo, dst_hi, op[4], bits[4]; };
-inline size_t off64(int32_t lo, int32_t hi) { return (size_t)(uint32_t)lo | ((size_t)(uint32_t)hi << 32); }
 inline float as_float(int32_t b) { float f; std::memcpy(&f, &b, 4); return f; }
 }  // namespace
 
@@ -21,8 +21,8 @@ int hp_resample_h_u8(const uint8_t* src, uint8_t* dst, const int32_t* jobs, int 
                      const int32_t* bounds, int C) {
   for (int i = 0; i < n_jobs; ++i) {
     const RJob& jb = reinterpret_cast<const RJob*>(jobs)[i];
-    const uint8_t* in = src + off64(jb.src_lo, jb.src_hi);
-    uint8_t* out = dst + off64(jb.dst_lo, jb.dst_hi);
+    const uint8_t* in = src + bbd_join64(jb.src_lo, jb.src_hi);
+    uint8_t* out = dst + bbd_join64(jb.dst_lo, jb.dst_hi);
     for (int row = 0; row < jb.in_h; ++row)
       for (int x = 0; x < jb.out_size; ++x) {
         const int xmin = bounds[jb.bounds_off + 2 * x], xmax = bounds[jb.bounds_off + 2 * x + 1];
@@ -44,8 +44,8 @@ int hp_resample_v_u8(const uint8_t* src, uint8_t* dst, const int32_t* jobs, int 
                      const int32_t* bounds, int C) {
   for (int i = 0; i < n_jobs; ++i) {
     const RJob& jb = reinterpret_cast<const RJob*>(jobs)[i];
-    const uint8_t* in = src + off64(jb.src_lo, jb.src_hi);
-    uint8_t* out = dst + off64(jb.dst_lo, jb.dst_hi);
+    const uint8_t* in = src + bbd_join64(jb.src_lo, jb.src_hi);
+    uint8_t* out = dst + bbd_join64(jb.dst_lo, jb.dst_hi);
     const size_t rb = (size_t)jb.in_w * C;
     for (int y = 0; y < jb.out_size; ++y) {
       const int ymin = bounds[jb.bounds_off + 2 * y], ymax = bounds[jb.bounds_off + 2 * y + 1];
@@ -64,8 +64,8 @@ int hp_color_jitter_u8(const uint8_t* src, float* dst, const int32_t* jobs, int 
   const size_t npx = (size_t)H * W;
   for (int i = 0; i < n_jobs; ++i) {
     const JJob& jb = reinterpret_cast<const JJob*>(jobs)[i];
-    const uint8_t* in = src + off64(jb.src_lo, jb.src_hi);
-    float* out = dst + off64(jb.dst_lo, jb.dst_hi);
+    const uint8_t* in = src + bbd_join64(jb.src_lo, jb.src_hi);
+    float* out = dst + bbd_join64(jb.dst_lo, jb.dst_hi);
     int cs = 4;
     for (int s = 0; s < 4; ++s)
       if (jb.op[s] == BBD_JIT_CONTRAST) { cs = s; break; }
@@ -96,8 +96,8 @@ int hp_u8_to_float_chw(const uint8_t* src, float* dst, const int32_t* jobs, int 
   const size_t npx = (size_t)H * W;
   for (int i = 0; i < n_jobs; ++i) {
     const int32_t* jb = jobs + (size_t)i * BBD_CONVERT_JOB;
-    const uint8_t* in = src + off64(jb[0], jb[1]);
-    float* out = dst + off64(jb[2], jb[3]);
+    const uint8_t* in = src + bbd_join64(jb[0], jb[1]);
+    float* out = dst + bbd_join64(jb[2], jb[3]);
     for (size_t p = 0; p < npx; ++p)
       for (int c = 0; c < 3; ++c) out[c * npx + p] = (float)in[3 * p + c] / 255.0f;
   }

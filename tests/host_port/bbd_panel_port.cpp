@@ -6,11 +6,10 @@
 
 #include "../../include/bbd_hip.h"
 #include "../../baseboostdepth_amd/csrc/bbd_panel_math.h"
+#include "../../baseboostdepth_amd/csrc/bbd_ragged_math.h"
 
 namespace {
-const void* address(int32_t lo, int32_t hi) {
-  return reinterpret_cast<const void*>((uintptr_t)(uint32_t)lo | ((uintptr_t)(uint32_t)hi << 32));
-}
+const void* address(int32_t lo, int32_t hi) { return reinterpret_cast<const void*>(bbd_join64(lo, hi)); }
 }  // namespace
 
 extern "C" int hp_train_panel_scratch_ints(int n_tiles) { return n_tiles > 0 && n_tiles <= 65535 ? 2 * n_tiles : 0; }
@@ -23,8 +22,7 @@ extern "C" int hp_train_panel(const int32_t* desc, const float* pose, const uint
   if ((long long)H * W > lim || (long long)rows * H > lim || (long long)cols * W > lim) return BBD_E_BADARG;
   if ((long long)rows * cols > 65535 || n_tiles > 65535) return BBD_E_BADARG;
   uint32_t packed[BBD_PANEL_LUT_ROWS];
-  for (int i = 0; i < BBD_PANEL_LUT_ROWS; ++i)
-    packed[i] = (uint32_t)lut[3 * i] | ((uint32_t)lut[3 * i + 1] << 8) | ((uint32_t)lut[3 * i + 2] << 16);
+  for (int i = 0; i < BBD_PANEL_LUT_ROWS; ++i) packed[i] = bbd_pack_rgb(lut + 3 * i);
   const BbdDims dm = bbd_dims(H, W);
   const size_t hw = (size_t)H * (size_t)W, out_row = (size_t)cols * (size_t)W;
   memset(out, 0, (size_t)rows * H * out_row * 3);
@@ -60,8 +58,7 @@ extern "C" int hp_train_panel(const int32_t* desc, const float* pose, const uint
         } else if (kind == BBD_PANEL_ARGMIN) {
           c = bbd_panel_argmin_colour(packed + 512, static_cast<const uint8_t*>(src)[i], p0, p1);
         }
-        uint8_t* o = out + (((size_t)row * H + y) * out_row + (size_t)col * W + x) * 3;
-        o[0] = (uint8_t)c; o[1] = (uint8_t)(c >> 8); o[2] = (uint8_t)(c >> 16);
+        bbd_put_rgb(out + (((size_t)row * H + y) * out_row + (size_t)col * W + x) * 3, c);
       }
   }
   return 0;

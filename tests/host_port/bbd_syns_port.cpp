@@ -9,6 +9,7 @@
 
 #include "../../include/bbd_hip.h"
 #include "../../baseboostdepth_amd/csrc/bbd_eval_math.h"
+#include "../../baseboostdepth_amd/csrc/bbd_ragged_math.h"
 #include "../../baseboostdepth_amd/csrc/bbd_syns_math.h"
 
 namespace {
@@ -19,11 +20,11 @@ struct Img {
 };
 
 Img load_img(const int32_t* desc, int i, int px_stride) {
-  const int32_t* d = desc + (size_t)i * BBD_EVAL_DESC;
+  const BbdEvalRow row = bbd_eval_row(desc, i);
   Img m;
-  m.off = (size_t)(uint32_t)d[0] | ((size_t)(uint32_t)d[1] << 32);
-  m.GH = d[2];
-  m.GW = d[3];
+  m.off = row.off;
+  m.GH = row.GH;
+  m.GW = row.GW;
   const bool ok = m.GH >= 1 && m.GW >= 1 && (long)m.GH * m.GW <= (long)px_stride;
   m.npx = ok ? m.GH * m.GW : 0;
   return m;

@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "../../include/bbd_hip.h"
+#include "../../baseboostdepth_amd/csrc/bbd_ragged_math.h"
 #include "../../baseboostdepth_amd/csrc/bbd_velo_math.h"
 
 extern "C" int hp_velo_depth_scratch_ints(int total_pixels, int n_frames) {
@@ -21,7 +22,7 @@ extern "C" int hp_velo_depth(const float* points, const int32_t* desc, const dou
   std::memset(scratch, 0, (size_t)scratch_ints * sizeof(int32_t));
   for (int f = 0; f < n_frames; ++f) {
     const int32_t* d = desc + (size_t)f * BBD_VELO_DESC;
-    const size_t off = (size_t)(uint32_t)d[0] | ((size_t)(uint32_t)d[1] << 32);
+    const size_t off = bbd_join64(d[0], d[1]);
     const int h = d[2], w = d[3], n = d[4];
     const long poff = d[5], soff = d[6], npx = (long)h * w;
     if (h < 1 || w < 1 || n < 0 || n > max_points || poff < 0 || soff < 0 || 4 * (soff + npx) > scratch_ints) return BBD_E_BADARG;

@@ -6,6 +6,7 @@
 
 #include "../../include/bbd_hip.h"
 #include "../../baseboostdepth_amd/csrc/bbd_math.h"
+#include "../../baseboostdepth_amd/csrc/bbd_ragged_math.h"
 #include "../../baseboostdepth_amd/csrc/bbd_viz_math.h"
 
 extern "C" int hp_disp_viz_scratch_ints(int n) { return n > 0 ? n : 0; }
@@ -18,7 +19,7 @@ extern "C" int hp_disp_viz(const float* disp, const int32_t* desc, const uint8_t
   const float lo = (float)min_disp, span = (float)(max_disp - min_disp), q = bbd_viz_quantile(percentile);
   for (int img = 0; img < n; ++img) {
     const int32_t* d = desc + (size_t)img * BBD_VIZ_DESC;
-    const size_t off = (size_t)(uint32_t)d[0] | ((size_t)(uint32_t)d[1] << 32);
+    const size_t off = bbd_join64(d[0], d[1]);
     const int H0 = d[2], W0 = d[3];
     const uint32_t npx = (uint32_t)H0 * (uint32_t)W0;
     if (npx == 0) continue;
@@ -52,9 +53,7 @@ extern "C" int hp_disp_viz(const float* disp, const int32_t* desc, const uint8_t
     float* st = stats + (size_t)img * 4;
     st[0] = vmin; st[1] = vmax; st[2] = lower; st[3] = upper;
     for (uint32_t i = 0; i < npx; ++i) {
-      const uint8_t* c = lut + 3 * bbd_viz_lut_index(s[i], vmin, vmax);
-      uint8_t* o = out_u8 + 3 * (off + i);
-      o[0] = c[0]; o[1] = c[1]; o[2] = c[2];
+      bbd_put_rgb(out_u8 + 3 * (off + i), bbd_pack_rgb(lut + 3 * bbd_viz_lut_index(s[i], vmin, vmax)));
       if (out_float) out_float[off + i] = s[i];
     }
   }

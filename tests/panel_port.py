@@ -6,26 +6,15 @@ table, LUT buffer, the trainer's tile layout) with the exact per-pixel arithmeti
 It extends `HostPortBackend`: every other launch goes to the port of the fused kernels, so a whole `Trainer` step and
 its log run on the host."""
 import ctypes
-import os
-import subprocess
 
 from host_port import HostPortBackend
+from port_build import build_port, call_port
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "host_port", "bbd_panel_port.cpp")
-LIB = os.path.join(HERE, "host_port", "libbbd_panel_port.so")
-CSRC = os.path.join(HERE, "..", "baseboostdepth_amd", "csrc")
-DEPS = [SRC, os.path.join(CSRC, "bbd_math.h"), os.path.join(CSRC, "bbd_viz_math.h"), os.path.join(CSRC, "bbd_panel_math.h"),
-        os.path.join(HERE, "..", "include", "bbd_hip.h")]
 PANEL_CALLS = ("bbd_train_panel", "bbd_argmin_hist")
 
 
 def build():
-    if os.path.isfile(LIB) and all(os.path.getmtime(LIB) >= os.path.getmtime(d) for d in DEPS):
-        return LIB
-    cmd = ["g++", "-O2", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-std=c++17", "-o", LIB, SRC]
-    subprocess.run(cmd, check=True)
-    return LIB
+    return build_port("libbbd_panel_port.so", ["bbd_panel_port.cpp"])
 
 
 class _Sizes:
@@ -46,9 +35,7 @@ class PanelPortBackend(HostPortBackend):
 
     def status(self, name, *args):
         """The port's return code (0 = done, < 0 = the ABI's argument errors)."""
-        fn = getattr(self.panel_dll, name.replace("bbd_", "hp_"))
-        fn.restype = ctypes.c_int
-        return fn(*[ctypes.c_int(a) if isinstance(a, int) else a for a in args])
+        return call_port(self.panel_dll, name, args)
 
     def run(self, name, anchor, *args):
         if name not in PANEL_CALLS:

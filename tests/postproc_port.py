@@ -4,23 +4,12 @@ Test infrastructure only, in the manner of tests/syns_port.py: `PostprocPortBack
 `baseboostdepth_amd.ops.post_process_disp`, so the CPU tier runs the product's Python plumbing (shape checks, the
 half split) with the exact per-pixel arithmetic of bbd_postproc.hip (bbd_postproc_math.h)."""
 import ctypes
-import os
-import subprocess
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "host_port", "bbd_postproc_port.cpp")
-LIB = os.path.join(HERE, "host_port", "libbbd_postproc_port.so")
-CSRC = os.path.join(HERE, "..", "baseboostdepth_amd", "csrc")
-DEPS = [SRC, os.path.join(CSRC, "bbd_math.h"), os.path.join(CSRC, "bbd_postproc_math.h"),
-        os.path.join(HERE, "..", "include", "bbd_hip.h")]
+from port_build import build_port, call_port
 
 
 def build():
-    if os.path.isfile(LIB) and all(os.path.getmtime(LIB) >= os.path.getmtime(d) for d in DEPS):
-        return LIB
-    cmd = ["g++", "-O2", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-std=c++17", "-o", LIB, SRC]
-    subprocess.run(cmd, check=True)
-    return LIB
+    return build_port("libbbd_postproc_port.so", ["bbd_postproc_port.cpp"])
 
 
 class PostprocPortBackend:
@@ -36,9 +25,7 @@ class PostprocPortBackend:
 
     def status(self, name, *args):
         """The port's return code (0 = done, < 0 = the ABI's argument errors)."""
-        fn = getattr(self.dll, name.replace("bbd_", "hp_"))
-        fn.restype = ctypes.c_int
-        return fn(*[ctypes.c_int(a) if isinstance(a, int) else a for a in args])
+        return call_port(self.dll, name, args)
 
     def run(self, name, anchor, *args):
         rc = self.status(name, *args)

@@ -5,23 +5,12 @@ Test infrastructure only, in the manner of tests/velo_port.py: `SynsPortBackend`
 `ops.chamfer_nn`, so the CPU tier runs the product's Python plumbing (descriptor tables, strides, scratch sizing, flags)
 with the exact per-pixel arithmetic of bbd_syns.hip (bbd_syns_math.h, bbd_eval_math.h)."""
 import ctypes
-import os
-import subprocess
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "host_port", "bbd_syns_port.cpp")
-LIB = os.path.join(HERE, "host_port", "libbbd_syns_port.so")
-CSRC = os.path.join(HERE, "..", "baseboostdepth_amd", "csrc")
-DEPS = [SRC, os.path.join(CSRC, "bbd_math.h"), os.path.join(CSRC, "bbd_eval_math.h"), os.path.join(CSRC, "bbd_syns_math.h"),
-        os.path.join(HERE, "..", "include", "bbd_hip.h")]
+from port_build import build_port, call_port
 
 
 def build():
-    if os.path.isfile(LIB) and all(os.path.getmtime(LIB) >= os.path.getmtime(d) for d in DEPS):
-        return LIB
-    cmd = ["g++", "-O2", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-std=c++17", "-o", LIB, SRC]
-    subprocess.run(cmd, check=True)
-    return LIB
+    return build_port("libbbd_syns_port.so", ["bbd_syns_port.cpp"])
 
 
 class _Sizes:
@@ -46,17 +35,7 @@ class SynsPortBackend:
 
     def status(self, name, *args):
         """The port's return code (0 = done, < 0 = the ABI's argument errors)."""
-        fn = getattr(self.dll, name.replace("bbd_", "hp_"))
-        fn.restype = ctypes.c_int
-        conv = []
-        for a in args:
-            if isinstance(a, float):
-                conv.append(ctypes.c_double(a))
-            elif isinstance(a, int):
-                conv.append(ctypes.c_int(a))
-            else:
-                conv.append(a)
-        return fn(*conv)
+        return call_port(self.dll, name, args)
 
     def run(self, name, anchor, *args):
         rc = self.status(name, *args)

@@ -87,6 +87,25 @@ def test_three_geometries_in_one_call_when_the_network_size_is_shared():
         viz_checks.check_stats(floats[i].cpu().numpy(), stats[i].cpu().numpy())
 
 
+TINY_SIZES = [(1, 1), (3, 5), (5, 7), (12, 40)]
+
+
+def test_tiny_ragged_batch_equals_the_host_port():
+    """One call, an 8 x 8 network output for four images: one pixel; 15 and 35 pixels (fewer than a workgroup has
+    threads, a last quad of three: byte stores); 480 pixels (two workgroups per histogram sweep, whole quads: packed
+    stores).  Colours, floats and stats equal the host port's bit for bit."""
+    from viz_port import VizPortBackend
+    from baseboostdepth_amd import ops
+    disp = torch.rand(4, 1, 8, 8, generator=torch.Generator().manual_seed(31))
+    colour, floats, stats = ops.disp_viz(disp.to(DEV), TINY_SIZES, want_float=True)
+    want_c, want_f, want_s = ops.disp_viz(disp, TINY_SIZES, want_float=True, backend=VizPortBackend())
+    assert np.array_equal(stats.cpu().numpy().view(np.uint32), want_s.numpy().view(np.uint32))
+    for i, size in enumerate(TINY_SIZES):
+        assert tuple(colour[i].shape) == size + (3,)
+        assert np.array_equal(floats[i].cpu().numpy().view(np.uint32), want_f[i].numpy().view(np.uint32)), size
+        assert np.array_equal(colour[i].cpu().numpy(), want_c[i].numpy()), size
+
+
 def _random_predictor(H=64, W=128, **kw):
     from baseboostdepth_amd import networks
     from baseboostdepth_amd.inference import DepthPredictor

@@ -139,3 +139,15 @@ def test_partial_skip_row_rule_on_the_callers_order_and_on_the_canonical_one():
     # the two orders do decide differently for some (sample, frame): the documented deviation of the canonical order
     by_m = lambda table, ms: {(ms[b], f): k for (b, f), k in table.items()}
     assert by_m(got, caller) != by_m(got_c, canon)
+
+
+def test_split64_words_fit_int32_and_join_back():
+    """Offsets travel to the kernels as two int32 words; the kernels join them as (uint32)lo | (uint32)hi << 32."""
+    import numpy as np
+    from baseboostdepth_amd import tables
+    for off in (0, 15, 2 ** 31 - 1, 2 ** 31, 2 ** 32 + 5, 2 ** 33):
+        lo, hi = tables.split64(off)
+        assert -2 ** 31 <= lo < 2 ** 31 and -2 ** 31 <= hi < 2 ** 31, off
+        assert tables.join64(lo, hi) == off
+        words = np.array([lo, hi], np.int32).view(np.uint32).astype(np.uint64)       # as a descriptor row stores them
+        assert int(words[0] | (words[1] << np.uint64(32))) == off
