@@ -6,7 +6,7 @@
 // the activation (profiles/r01/bench_md2_one_steady_step_v6.csv: 2.6 ms BN + ~1.3 ms add/ReLU per step).
 // Here the tail of a block is two launches each way over NCHW fp32:
 //
-//   forward : stats   per channel sum / sum of squares (fp64 partials, fixed-order combine)
+//   forward : stats   per channel sums of x - pivot and its square (centred fp32 runs, fp64 partials, fixed-order combine)
 //             apply   y = relu(gamma * (x - mean) * invstd + beta + residual); running stats updated
 //   backward: reduce  g = dy * (y > 0);  per channel sum(g), sum(g * xhat)
 //             apply   dx = gamma * invstd * (g - mean(g) - xhat * mean(g * xhat));  dresidual = g;
@@ -100,43 +100,75 @@ __device__ __forceinline__ void plane_slice(int HW, int split, int k, int* lo, i
 // Thread layout: 64 lanes sweep the slice, the 4 waves take every 4th image - a slice is only ~100 float4 long, so 256
 // lanes along it left most of them idle with one dependent load per image in flight.
 
-// forward statistics of slice k: block totals of x and x^2
+// The pivot of one (channel, group): its first element.  The totals that leave stats_slice are sums of (x - pivot) and
+// (x - pivot)^2, so that the subtraction in group_moments cancels digits of a deviation (about one standard deviation
+// for typical data, exactly 0 for a constant channel) and not of the mean.  A far-off pivot (an outlier in that very
+// place) costs digits of the double totals only - the fp32 part below never sees it.
+__device__ __forceinline__ double group_pivot(const BnArgs& a, int c, int grp) {
+  const int first = group_row(a, grp);
+  if (first >= group_row(a, grp + 1)) return 0.0;              // an empty group of a device-resident table
+  return (double)a.x[((size_t)first * a.C + c) * a.HW];
+}
+
+// forward statistics of slice k: block totals of (x - pivot) and (x - pivot)^2.
+// Squares of x itself, added up in fp32, lose (mean / std)^2 of the variance's digits however the runs are combined
+// afterwards.  So each lane keeps (count, mean, M2 = sum of squared deviations from that mean) of its run through one
+// image: a float4 is centred in registers (its own mean, the squared deviations of its four values) and merged by
+// Chan's update.  Its weights depend on the iteration count alone, 1 / j and 4 (j - 1) / j at the j-th float4, and the
+// reciprocal is the hardware's one-instruction approximation: both updates use the same w, so an ulp of it moves
+// mean and M2 by an ulp of a deviation.  At the end of the image the run becomes n * (mean - pivot) and M2 + n * (mean - pivot)^2 in
+// double.  M2 and the merged differences are deviations; the lane's mean is an fp32 number of the data's size, so the
+// hand-over carries its rounding, 2^-24 |mean| per run, into both totals (the cross term 2 (mean - pivot) * sum(x - mean)
+// is taken as 0).  That is the error fp32 x - mean has in the apply pass anyway, it has no preferred sign and averages
+// over the runs; it is what limits the variance once mean / std reaches the thousands.
 __device__ __forceinline__ void stats_slice(const BnArgs& a, int c, int grp, int split, int k, double* sh, double* ts,
                                             double* tss) {
   int lo, hi;
   plane_slice(a.HW, split, k, &lo, &hi);
-  float s = 0.0f, ss = 0.0f;
+  const double pivot = group_pivot(a, c, grp);
   double ds = 0.0, dss = 0.0;
   const bool vec = (a.HW & 3) == 0;
   const int lane = threadIdx.x & 63, sub = threadIdx.x >> 6;
   for (int n = group_row(a, grp) + sub; n < group_row(a, grp + 1); n += NT / 64) {
     const float* p = a.x + ((size_t)n * a.C + c) * a.HW;
+    float cnt = 0.0f, mean = 0.0f, m2 = 0.0f;
     if (vec) {
       for (int i = lo + 4 * lane; i < hi; i += 4 * 64) {
         const float4 v = *reinterpret_cast<const float4*>(p + i);
-        s += (v.x + v.y) + (v.z + v.w);
-        ss += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+        const float m4 = ((v.x + v.y) + (v.z + v.w)) * 0.25f;
+        const float dx = v.x - m4, dy = v.y - m4, dz = v.z - m4, dw = v.w - m4;
+        const float q4 = (dx * dx + dy * dy) + (dz * dz + dw * dw);
+        const float delta = m4 - mean;
+        const float w = __builtin_amdgcn_rcpf(cnt * 0.25f + 1.0f);       // 1 / j: exact at j = 1, 2, 4, ...
+        mean += delta * w;
+        m2 += q4 + (delta * delta) * (cnt * w);
+        cnt += 4.0f;
       }
     } else {
       for (int i = lo + lane; i < hi; i += 64) {
         const float v = p[i];
-        s += v;
-        ss += v * v;
+        const float delta = v - mean;
+        cnt += 1.0f;
+        mean += delta * __builtin_amdgcn_rcpf(cnt);
+        m2 += delta * (v - mean);
       }
     }
-    ds += (double)s; dss += (double)ss;     // short fp32 runs, fp64 across images
-    s = 0.0f; ss = 0.0f;
+    const double d = (double)mean - pivot;       // fp64 across images; cnt = 0 adds exact zeros
+    ds += (double)cnt * d;
+    dss += (double)m2 + (double)cnt * d * d;
   }
   *ts = block_sum(ds, sh);
   *tss = block_sum(dss, sh);
 }
 
-// mean / invstd of one (channel, group) from its totals
-__device__ __forceinline__ void group_moments(const BnArgs& a, int grp, double ts, double tss, double* mean, double* var) {
+// mean / variance of one (channel, group) from its totals about the pivot
+__device__ __forceinline__ void group_moments(const BnArgs& a, int c, int grp, double ts, double tss, double* mean,
+                                              double* var) {
   const double cnt = (double)(group_row(a, grp + 1) - group_row(a, grp)) * (double)a.HW;
   if (!(cnt > 0.0)) { *mean = 0.0; *var = 0.0; return; }      // an empty group of a device-resident table
-  *mean = ts / cnt;
-  double v = tss / cnt - (*mean) * (*mean);
+  const double off = ts / cnt;
+  *mean = group_pivot(a, c, grp) + off;
+  double v = tss / cnt - off * off;
   *var = v > 0.0 ? v : 0.0;
 }
 // running statistics: one momentum update per group, in group order = the order of the calls replaced.
@@ -149,7 +181,7 @@ __device__ __forceinline__ void update_running(const BnArgs& a, int c, Totals to
     for (int q = 0; q < tracked; ++q) {
       double qs, qss, qmean, qvar;
       totals(q, &qs, &qss);
-      group_moments(a, q, qs, qss, &qmean, &qvar);
+      group_moments(a, c, q, qs, qss, &qmean, &qvar);
       const double qcnt = (double)(group_row(a, q + 1) - group_row(a, q)) * (double)a.HW;
       const double unbiased = qcnt > 1.0 ? qvar * qcnt / (qcnt - 1.0) : qvar;
       rm = (1.0f - a.momentum) * rm + a.momentum * (float)qmean;
@@ -325,7 +357,7 @@ __global__ __launch_bounds__(NT) void bn_apply_kernel(BnArgs a) {
   if (threadIdx.x == 0) {
     double ts, tss, mean, var;
     group_totals(a, c, grp, &ts, &tss);
-    group_moments(a, grp, ts, tss, &mean, &var);
+    group_moments(a, c, grp, ts, tss, &mean, &var);
     const float invstd = (float)(1.0 / sqrt(var + (double)a.eps));
     s_mean = (float)mean;
     s_scale = a.gamma[c] * invstd;
@@ -396,7 +428,7 @@ __global__ __launch_bounds__(NT) void bn_fwd_small_kernel(BnArgs a) {
   }
   if (threadIdx.x == 0) {
     double mean, var;
-    group_moments(a, grp, ts, tss, &mean, &var);
+    group_moments(a, c, grp, ts, tss, &mean, &var);
     const float invstd = (float)(1.0 / sqrt(var + (double)a.eps));
     s_mean = (float)mean;
     s_scale = a.gamma[c] * invstd;

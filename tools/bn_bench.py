@@ -37,8 +37,9 @@ for name, C, H, W, res in shapes:
         torch.cuda.synchronize()
         be.timer = None
         s = timer.summary()
-        fwd = s["bbd_bn_act_grouped_fwd"][1] * 1e3
-        bwd = s["bbd_bn_act_grouped_bwd"][1] * 1e3
+        # (KernelTimer files the grouped launches under the plain entry points' names)
+        fwd = s["bbd_bn_act_fwd"][1] * 1e3
+        bwd = s["bbd_bn_act_bwd"][1] * 1e3
         t = N * C * H * W * 4
         fb = t * (3 + (1 if res else 0))
         bb = t * ((2 + (1 if res else 0)) * 2 + 1 + (1 if res else 0))
