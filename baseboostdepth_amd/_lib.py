@@ -20,7 +20,7 @@ PROJ_STRIDE = 24
 KIND_WARP, KIND_IDENT, FLAG_NO_POSE_GRAD = 0, 1, 0x100
 COMPOSE_STRIDE, COMPOSE_ERROR, COMPOSE_REPLACE = 12, 1, 2
 PAIR_SHIFT = 16        # bits 16-23 of bbd_cand_t.kind: 1 + index of the pass partner (hint), 0 = none
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 _p = ctypes.c_void_p
 _i = ctypes.c_int
@@ -73,6 +73,7 @@ SIGNATURES = {
     "bbd_chamfer_nn": [_p, _p, _i, _i, _p, _p, _p],
     "bbd_syns_pointcloud": [_p] * 6 + [_i, _p] + [_i] * 6 + [_d] * 5 + [_i, _p],
     "bbd_pose_ate": [_p] * 6 + [_i] * 4 + [_p],
+    "bbd_pose_trajectory": [_p] * 11 + [_i] * 5 + [_p],
     "bbd_post_process_disp": [_p, _p, _i, _i, _i, _p],
     "bbd_train_panel_scratch_ints": [_i],
     "bbd_train_panel": [_p] * 6 + [_i] * 6 + [_p],
@@ -131,6 +132,8 @@ VIZ_DESC = 4
 PANEL_DESC, PANEL_COLOR, PANEL_WARP, PANEL_SCALAR, PANEL_ARGMIN, PANEL_LUT_ROWS = 8, 0, 1, 2, 3, 532
 VELO_DESC, VELO_VEL_DEPTH = 8, 1
 SYNS_OUT, SYNS_CLOUD_OUT, SYNS_RAYS_PIXEL = 8, 8, 8
+TRAJ_MAX_LEN = 8                                                 # BBD_TRAJ_MAX_LEN
+TRAJ_MODES = {"sim3": 0, "se3": 1, "scale": 2, "none": 3}      # BBD_TRAJ_SIM3 .. BBD_TRAJ_NONE
 EVAL_PRED_IS_DISP, EVAL_MEDIAN_MIDPOINT, EVAL_NO_MEDIAN_SCALING = 1, 2, 4
 ERROR_MAP_MAX_RADIUS = 4
 

@@ -31,6 +31,7 @@ SRCS = _here("""
     bbd_velo.hip
     bbd_syns.hip
     bbd_odom.hip
+    bbd_traj.hip
     bbd_postproc.hip
     bbd_panel.hip
     bbd_compare.hip

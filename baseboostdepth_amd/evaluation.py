@@ -13,7 +13,9 @@ distance maps), `edge_metrics` (edge accuracy / completeness and `err`), `pointc
 back-projected clouds, all-pairs nearest neighbour) and `syns_metrics`, the reference's 9-column row.
 
 The KITTI odometry evaluation (evaluate_pose.py) is `pose_ate` - chained poses, local ground truth, the trajectory error
-of every track and its mean / std in one `bbd_pose_ate` call - and `evaluate_pose`, the evaluator above it.
+of every track and its mean / std in one `bbd_pose_ate` call - `pose_trajectory` - the whole trajectory chained from the
+single steps, aligned to ground truth, with the devkit's t_rel / r_rel and the aligned ATE in one `bbd_pose_trajectory`
+call - and `evaluate_pose`, the evaluator above them.
 """
 import collections
 
@@ -23,7 +25,7 @@ import torch
 from . import ops
 from .tables import split64, upload
 from ._lib import (EVAL_DESC, EVAL_OUT, EVAL_PRED_IS_DISP, EVAL_MEDIAN_MIDPOINT, EVAL_NO_MEDIAN_SCALING, SYNS_OUT,
-                   SYNS_CLOUD_OUT, SYNS_RAYS_PIXEL, BbdError, ptr)
+                   SYNS_CLOUD_OUT, SYNS_RAYS_PIXEL, TRAJ_MAX_LEN, TRAJ_MODES, BbdError, ptr)
 
 METRIC_NAMES = ["de/abs_rel", "de/sq_rel", "de/rms", "de/log_rms", "da/a1", "da/a2", "da/a3"]   # trainer.py:156
 GARG_CROP = (0.40810811, 0.99189189, 0.03594771, 0.96405229)     # trainer.py:603-604
@@ -588,6 +590,87 @@ def pose_ate_into(poses, gt, chained, gt_local, ates, summary, skip, track_lengt
                 N, M, int(skip), int(track_length))
 
 
+KITTI_LENGTHS = (100.0, 200.0, 300.0, 400.0, 500.0, 600.0, 700.0, 800.0)     # the devkit's sub-sequence lengths, metres
+PoseTrajectory = collections.namedtuple("PoseTrajectory", "traj gt_traj aligned transform dist pairs per_length summary")
+PoseTrajectory.__doc__ = """Result of `pose_trajectory`, float64 device tensors, F = J + 1 frames: `traj` [F,4,4] (camera to
+first frame, chained from the steps), `gt_traj` [F,4,4] (inv(G_0) G_j), `aligned` [F,4,4], `transform` [4,4] (R | t),
+`dist` [F] (ground-truth path length), `pairs` [ceil(F/step), n_len, 4] = (last or -1, t_err, r_err, 0), `per_length`
+[n_len, 3] = (mean t_err, mean r_err, count), `summary` [8] = (t_rel, r_rel, pair count, ate_rmse, ate_mean, ate_max,
+c, F).  t_err is per unit of length (x 100 = %), r_err in radians per unit of length."""
+
+
+def _traj_lengths(lengths):
+    import ctypes
+    lengths = [float(x) for x in lengths]
+    if not 1 <= len(lengths) <= TRAJ_MAX_LEN or not all(np.isfinite(x) and x > 0 for x in lengths) \
+            or any(b <= a for a, b in zip(lengths, lengths[1:])):
+        raise ValueError("pose_trajectory: lengths must be 1 to %d positive, strictly increasing numbers, got %r"
+                         % (TRAJ_MAX_LEN, lengths))
+    return (ctypes.c_double * len(lengths))(*lengths)
+
+
+def pose_trajectory(steps, gt_global, align="sim3", lengths=KITTI_LENGTHS, step=10, backend=None):
+    """The KITTI devkit's odometry scores of a whole sequence in ONE `bbd_pose_trajectory` call (four small launches, no
+    host synchronisation): `steps` float32 [J,4,4] (or [J,16]) are the pose network's matrices of the
+    frame pairs (j, j+1) - section 1 of `pose_ate`'s `poses` with skip 1 - and `gt_global` [M,12] (or [M,3,4]) float64
+    the rows of the poses file, M >= J + 1.  The steps are chained into a trajectory, aligned to ground truth
+    (`align`: "sim3" Umeyama, "se3" rigid, "scale" the reference's least-squares scale only, "none"), and scored: the ATE
+    of the aligned trajectory and, for first frames 0, `step`, 2 `step`, .. and every length of `lengths`, the devkit's
+    translational and rotational sub-sequence errors.  Returns a `PoseTrajectory`.  A prediction that never moves has no
+    scale: c and everything that depends on it are NaN under "sim3" and "scale"."""
+    backend = backend or ops.default_backend()
+    if align not in TRAJ_MODES:
+        raise ValueError("pose_trajectory: align must be one of %s, got %r" % (", ".join(TRAJ_MODES), align))
+    step = int(step)
+    if step < 1:
+        raise ValueError("pose_trajectory: step must be at least 1 (got %d)" % step)
+    clen = _traj_lengths(lengths)
+    steps = steps.detach()
+    if steps.dtype != torch.float32 or steps.dim() not in (2, 3) or tuple(steps.shape[1:]) not in ((16,), (4, 4)) \
+            or steps.shape[0] < 1:
+        raise ValueError("pose_trajectory: steps must be float32 [J >= 1, 4, 4], got %s %s"
+                         % (steps.dtype, tuple(steps.shape)))
+    dev = steps.device
+    J = steps.shape[0]
+    F = J + 1
+    steps = steps.reshape(J, 16).contiguous()
+    gt = torch.as_tensor(gt_global, dtype=torch.float64).reshape(-1, 12)
+    M = gt.shape[0]
+    if M < F:
+        raise ValueError("pose_trajectory: %d steps span %d frames, the ground truth has %d poses (M = %d < J + 1 = %d)"
+                         % (J, F, M, M, F))
+    if gt.device != dev:
+        gt = upload(gt, dev)
+    gt = gt.contiguous()
+    backend._check(steps, gt)
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=dev)   # noqa: E731
+    res = PoseTrajectory(new(F, 4, 4), new(F, 4, 4), new(F, 4, 4), new(4, 4), new(F), new(-(-F // step), len(clen), 4),
+                         new(len(clen), 3), new(8))
+    pose_trajectory_into(steps, gt, clen, res, step, align, backend)
+    return res
+
+
+def pose_trajectory_into(steps, gt, lengths, out, step, align, backend=None):
+    """The `bbd_pose_trajectory` call itself on caller-owned, contiguous tensors of one device: `out` is a
+    `PoseTrajectory` (or any sequence of its eight tensors, shapes as `pose_trajectory` builds them), `lengths` a
+    sequence of numbers or a ctypes double array; every element of the eight outputs is written, nothing else is."""
+    import ctypes
+    backend = backend or ops.default_backend()
+    if not isinstance(lengths, ctypes.Array):
+        lengths = _traj_lengths(lengths)
+    J, M, F, n_len = steps.shape[0], gt.shape[0], steps.shape[0] + 1, len(lengths)
+    traj, gt_traj, aligned, transform, dist, pairs, per_length, summary = out
+    assert steps.dtype == torch.float32 and steps.numel() == J * 16 and gt.dtype == torch.float64 and gt.numel() == M * 12
+    assert all(t.dtype == torch.float64 for t in out)
+    assert traj.numel() == F * 16 and gt_traj.numel() == F * 16 and aligned.numel() == F * 16 and transform.numel() == 16
+    assert dist.numel() == F and pairs.numel() == -(-F // int(step)) * n_len * 4 and per_length.numel() == n_len * 3
+    assert summary.numel() == 8
+    backend._check(steps, gt, *out)
+    backend.run("bbd_pose_trajectory", summary, ptr(steps), ptr(gt), ctypes.cast(lengths, ctypes.c_void_p), ptr(traj),
+                ptr(gt_traj), ptr(aligned), ptr(transform), ptr(dist), ptr(pairs), ptr(per_length), ptr(summary), J, M,
+                n_len, int(step), TRAJ_MODES[align])
+
+
 def odom_sequence(eval_split):
     """`odom_<n>` -> n (evaluate_pose.py:50-53; every sequence with ground truth, 0-10, is accepted)."""
     parts = str(eval_split).split("_")
@@ -607,7 +690,7 @@ def odom_paths(opt):
             os.path.join(root, "poses", "{:02d}.txt".format(seq)))
 
 
-def evaluate_pose(opt, dataloader=None, gt_poses=None, models=None, batch_windows=64):
+def evaluate_pose(opt, dataloader=None, gt_poses=None, models=None, batch_windows=64, backend=None, device=None):
     """The reference's `evaluate_pose.py`: the pose network's direct `skip_frame`-step pose and the pose chained from its
     single steps, scored against KITTI odometry ground truth (absolute trajectory error over `track_length`-pose tracks).
     Prints the reference's two `Trajectory error` lines, direct first, and returns a dict: `ate_mean`, `ate_std`,
@@ -624,14 +707,29 @@ def evaluate_pose(opt, dataloader=None, gt_poses=None, models=None, batch_window
     `opt.splits_dir/odom/test_files_<nn>.txt`, frames and `poses/<nn>.txt` come from `opt.odom_path` (default
     `dirname(opt.kt_path)/odom`) and weights from `pose_encoder.pth` / `pose.pth` in `opt.load_weights_folder`.
     Departures from the reference, both deliberate: only TRAILING windows without frames are dropped (a frame missing
-    in the middle raises), and the input size is `opt.height x opt.width` (the reference fixes 192 x 640, the defaults)."""
+    in the middle raises), and the input size is `opt.height x opt.width` (the reference fixes 192 x 640, the defaults).
+
+    `opt.trajectory` adds the scores every KITTI odometry table reports (`pose_trajectory`), with no
+    further network pass: the N + S - 1 single steps of the sequence are taken from the pose buffer - `poses[1][j]` for
+    j < N, then `poses[1 + k][N - 1]` for k = 1 .. S - 1 - chained, aligned by `opt.trajectory_align` and scored; the
+    results travel in the same read-back.  One more line is printed after the reference's two (alignment, frames, t_rel
+    in %, r_rel in deg / 100 m, the ATE rmse in metres, the scale) and the dict gains `t_rel` (a fraction), `r_rel`
+    (rad / m), `traj_ate_rmse`, `traj_scale`, `per_length` ([8, 3]: mean t_err, mean r_err, count for 100 .. 800 m),
+    `traj_aligned` and `traj_gt` ([F,4,4]).  `opt.save_trajectory` writes the aligned poses as a KITTI poses file.
+    `backend` / `device` are the seam of the test tier (default: the HIP backend on `cuda:<opt.cuda>`)."""
     import os
     from . import datasets, networks, tuning
     tuning.use_shipped_db()
     seq, split_file, odom_root, poses_file = odom_paths(opt)
     S, L = int(getattr(opt, "skip_frame", 2)), int(getattr(opt, "track_length", 1))
-    device = torch.device("cuda:%d" % getattr(opt, "cuda", 0))
+    device = torch.device(device if device is not None else "cuda:%d" % getattr(opt, "cuda", 0))
     height, width = opt.height, opt.width
+    trajectory, save_trajectory = bool(getattr(opt, "trajectory", False)), getattr(opt, "save_trajectory", None)
+    align = getattr(opt, "trajectory_align", "sim3")
+    if save_trajectory and not trajectory:
+        raise ValueError("evaluate_pose: --save_trajectory needs --trajectory")
+    if trajectory and align not in TRAJ_MODES:
+        raise ValueError("evaluate_pose: --trajectory_align must be one of %s, got %r" % (", ".join(TRAJ_MODES), align))
     # ---- host: the window tables and the ground truth, checked before anything is launched
     lines = datasets.KITTIOdomDataset(datasets.readlines(split_file), 0, height, width, kt_path=opt.kt_path, is_train=False,
                                       kt=True, naive_mix=True, odom_path=odom_root)
@@ -676,19 +774,41 @@ def evaluate_pose(opt, dataloader=None, gt_poses=None, models=None, batch_window
         for lo in range(0, N, max(1, int(batch_windows))):
             chunk = table[:, :, lo:lo + batch_windows]
             n = chunk.shape[2]
-            x = ops.gather_pairs(pool, chunk[0].reshape(-1), chunk[1].reshape(-1))               # [(1+S) n, 6, H, W]
+            x = ops.gather_pairs(pool, chunk[0].reshape(-1), chunk[1].reshape(-1), backend=backend)  # [(1+S) n, 6, H, W]
             axisangle, translation = decoder([encoder(x)])
-            mats = ops.pose_matrix(axisangle[:, 0], translation[:, 0])
+            mats = ops.pose_matrix(axisangle[:, 0], translation[:, 0], backend=backend)
             poses[:, lo:lo + n] = mats.view(1 + S, n, 16)
-        res = pose_ate(poses, gt_poses, skip=S, track_length=L)
-        packed = torch.cat([res.summary.reshape(-1), res.ates.reshape(-1), res.direct.reshape(-1).double(),
-                            res.chained.reshape(-1).double()])               # float32 -> float64 and back is exact
+        if trajectory:
+            gt_poses = upload(gt_poses, device)          # one upload for both calls
+        res = pose_ate(poses, gt_poses, skip=S, track_length=L, backend=backend)
+        parts = [res.summary.reshape(-1), res.ates.reshape(-1), res.direct.reshape(-1).double(),
+                 res.chained.reshape(-1).double()]                           # float32 -> float64 and back is exact
+        if trajectory:
+            if N < 1:
+                raise ValueError("evaluate_pose: --trajectory needs at least one window")
+            # frame pair (j, j+1): window j's first step, and past the last window its later steps
+            steps = torch.cat([poses[1], poses[2:, N - 1]]) if S > 1 else poses[1]
+            tr = pose_trajectory(steps, gt_poses, align=align, backend=backend)
+            parts += [tr.summary, tr.per_length.reshape(-1), tr.aligned.reshape(-1), tr.gt_traj.reshape(-1)]
+        packed = torch.cat(parts)
     host = packed.cpu().numpy()                          # the only host synchronisation: the finished tables
     tracks = res.ates.shape[1]
     summary, ates = host[:8].reshape(2, 4), host[8:8 + 2 * tracks].reshape(2, tracks)
-    mats = host[8 + 2 * tracks:].astype(np.float32).reshape(2, N, 4, 4)
+    mats = host[8 + 2 * tracks:8 + 2 * tracks + 32 * N].astype(np.float32).reshape(2, N, 4, 4)
     out = {"ate_mean": float(summary[0, 0]), "ate_std": float(summary[0, 1]), "ate_chained_mean": float(summary[1, 0]),
            "ate_chained_std": float(summary[1, 1]), "ates": ates, "pred_poses": mats[0], "pred_poses_chained": mats[1]}
     print("\n   Trajectory error: {:0.3f}, std: {:0.3f}\n".format(out["ate_mean"], out["ate_std"]))
     print("\n   Trajectory error: {:0.3f}, std: {:0.3f}\n".format(out["ate_chained_mean"], out["ate_chained_std"]))
+    if trajectory:
+        rest = host[8 + 2 * tracks + 32 * N:]
+        n_len, frames_scored = len(KITTI_LENGTHS), N + S
+        tsum, per_length = rest[:8], rest[8:8 + 3 * n_len].reshape(n_len, 3)
+        both = rest[8 + 3 * n_len:].reshape(2, frames_scored, 4, 4)
+        out.update({"t_rel": float(tsum[0]), "r_rel": float(tsum[1]), "traj_ate_rmse": float(tsum[3]),
+                    "traj_scale": float(tsum[6]), "per_length": per_length, "traj_aligned": both[0], "traj_gt": both[1]})
+        print("   Full trajectory ({}, {:d} frames): t_rel {:0.3f} %, r_rel {:0.3f} deg/100m, ATE {:0.3f} m, scale {:0.4f}\n"
+              .format(align, frames_scored, 100.0 * out["t_rel"], 100.0 * np.degrees(out["r_rel"]), out["traj_ate_rmse"],
+                      out["traj_scale"]))
+        if save_trajectory:
+            np.savetxt(save_trajectory, both[0].reshape(frames_scored, 16)[:, :12], fmt="%.6e")
     return out

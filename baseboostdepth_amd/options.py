@@ -86,6 +86,13 @@ class MonodepthOptions:
                                  help="KITTI odometry root (sequences/, poses/); default dirname(kt_path)/odom")
         self.parser.add_argument("--skip_frame", type=int, default=2)
         self.parser.add_argument("--track_length", type=int, default=1)
+        # the scores of the KITTI odometry tables: the whole trajectory chained from the single steps
+        self.parser.add_argument("--trajectory", action="store_true",
+                                 help="also print t_rel (%%), r_rel (deg/100m) and the ATE of the aligned full trajectory")
+        self.parser.add_argument("--trajectory_align", type=str, default="sim3", choices=["sim3", "se3", "scale", "none"],
+                                 help="alignment of the predicted trajectory to ground truth before it is scored")
+        self.parser.add_argument("--save_trajectory", type=str, default=None,
+                                 help="with --trajectory: write the aligned poses to this file, 12 numbers per row")
 
     def parse(self, argv=None):
         self.options = self.parser.parse_args(argv)

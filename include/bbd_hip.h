@@ -38,8 +38,9 @@ extern "C" {
  * 9 = bbd_velo_depth / bbd_velo_depth_scratch_ints (ground-truth depth maps from Velodyne scans);
  * 10 = bbd_syns_* / bbd_chamfer_nn (SYNS-Patches evaluation: edge and point-cloud metrics);
  * 11 = bbd_pose_ate (KITTI odometry evaluation: chained poses, local ground truth, trajectory error);
- * 12 = bbd_post_process_disp (depth evaluation: flip post-processing of the predicted disparities). */
-#define BBD_ABI_VERSION 13
+ * 12 = bbd_post_process_disp (depth evaluation: flip post-processing of the predicted disparities);
+ * 14 = bbd_pose_trajectory (KITTI odometry: full-trajectory t_rel, r_rel and aligned ATE). */
+#define BBD_ABI_VERSION 14
 
 /* Source frames live in separate tensors, one per frame id (inputs[("color", f, 0)],
  * trainer.py:428).  A "slot" indexes a host array of their base pointers. */
@@ -503,6 +504,38 @@ int bbd_post_process_disp(const float* disp, float* out, int n, int h, int w, vo
  * S < 1, L < 1, N < 0 or N > M - S return BBD_E_BADARG.  An output without elements may be NULL. */
 int bbd_pose_ate(const float* poses, const double* gt, float* chained, double* gt_local, double* ates, double* summary,
                  int N, int M, int S, int L, void* stream);
+
+/* ---- KITTI odometry, the whole trajectory: the trajectory chained from the network's single steps, its
+ * alignment to ground truth, the ATE of the aligned trajectory and the devkit's sub-sequence errors (calcSequenceErrors)
+ * in one call - four small launches on `stream`, no allocation, no host synchronisation, no atomics (identical calls
+ * give identical bytes).  Arithmetic and its order: csrc/bbd_traj_math.h.  F = J + 1 frames.
+ *   steps      float32 [J, 16]: steps[j] = the network's pose matrix of the frame pair (j, j+1), in the convention of
+ *              bbd_pose_ate's gt_local with skip 1: it plays the role of inv(inv(G_j) . G_{j+1})
+ *   gt         float64 [M, 12], M >= F: the rows of the KITTI poses file; rows past F are not read
+ *   lengths    HOST float64 [n_len], 1 <= n_len <= BBD_TRAJ_MAX_LEN, positive, finite and strictly increasing: the
+ *              sub-sequence lengths in the unit of gt (the devkit: 100 .. 800 m); read before the call returns
+ *   traj       float64 [F, 16] out: C_0 = I, C_{j+1} = C_j . inv(steps[j]) (general inverse, left to right)
+ *   gt_traj    float64 [F, 16] out: inv(G_0) . G_j
+ *   aligned    float64 [F, 16] out: [R R_j | c R p_j + t] over (0 0 0 1)
+ *   transform  float64 [16] out: [R | t] over (0 0 0 1); the scale c is summary[6]
+ *   dist       float64 [F] out: the ground truth's path length up to frame j, non-decreasing
+ *   pairs      float64 [ceil(F / step), n_len, 4] out: for first = 0, step, 2 step .. and every length (last, t_err, r_err,
+ *              0), errors per unit of length and in radians per unit of length; no frame far enough: (-1, NaN, NaN, 0)
+ *   per_length float64 [n_len, 3] out: mean t_err, mean r_err, count of the length's valid pairs
+ *   summary    float64 [8] out: t_rel, r_rel (means over all valid pairs), their count, ate_rmse, ate_mean, ate_max, c, F
+ *   mode       BBD_TRAJ_SIM3 (Umeyama), _SE3 (the same with c = 1), _SCALE (R = I, t = 0, c = sum g.p / sum p.p) or _NONE
+ * A mean without a pair is NaN; a prediction that never moves makes c = 0/0 = NaN under SIM3 and SCALE, and every
+ * number that depends on c with it.  Every NaN is 0x7ff8000000000000.  A NULL pointer, J < 1, M < J + 1, n_len outside
+ * [1, 8], step < 1, bad lengths or an unknown mode return BBD_E_BADARG, M > INT_MAX / 16 BBD_E_TOOMANY; nothing is
+ * launched then and no output is touched. */
+#define BBD_TRAJ_MAX_LEN 8
+#define BBD_TRAJ_SIM3 0
+#define BBD_TRAJ_SE3 1
+#define BBD_TRAJ_SCALE 2
+#define BBD_TRAJ_NONE 3
+int bbd_pose_trajectory(const float* steps, const double* gt, const double* lengths, double* traj, double* gt_traj,
+                        double* aligned, double* transform, double* dist, double* pairs, double* per_length,
+                        double* summary, int J, int M, int n_len, int step, int mode, void* stream);
 
 /* ---- Loader image pipeline: replaces the per-item Pillow/torchvision work of
  * datasets/mono_dataset.py:186-205 (Resize(LANCZOS) chain, ColorJitter, ToTensor) and the stacking of

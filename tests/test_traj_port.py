@@ -1,0 +1,289 @@
+"""CPU tier of the full-trajectory odometry scores: the host port of bbd_traj.hip (same bbd_traj_math.h) through the
+`backend=` seam of `evaluation.pose_trajectory` against the numpy reference (tests/traj_ref.py; acceptance rules:
+tests/traj_checks.py), the properties that pin the conventions (telescoping, c s = 1, independence of the relative
+errors from the rigid part of the alignment), the refusals, the new options, and `evaluation.evaluate_pose` end to end
+through the port with an injected dataloader and a stub pose network."""
+import ctypes
+import os
+import sys
+import types
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import traj_checks as tc  # noqa: E402
+import traj_ref as ref  # noqa: E402
+from traj_port import TrajPortBackend  # noqa: E402
+from baseboostdepth_amd import _lib, evaluation  # noqa: E402
+from baseboostdepth_amd.options import MonodepthOptions  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def port():
+    return TrajPortBackend()
+
+
+def test_the_reference_takes_the_branches_the_cases_are_there_for():
+    assert tc.reference("mirrored", "sim3")[0]["branch"] == -1.0 and tc.reference("noisy63", "sim3")[0]["branch"] == 1.0
+    planar = tc.make("planar")
+    assert (planar["gt"][:, 7] == 0).all()                                    # every y exactly 0
+    line = ref.gt_trajectory(tc.make("collinear")["gt"], 64)[:, :3, 3]
+    assert (line[:, :2] == 0).all() and np.ptp(line[:, 2]) > 50              # exactly straight: Sigma has rank 1
+    assert tc.reference("no_pair", "sim3")[0]["summary"][2] == 0 and tc.reference("single", "sim3")[0]["summary"][2] == 0
+    for name in ("noisy63", "noisy257", "noisy699"):
+        want = tc.reference(name, "sim3")[0]
+        assert (want["per_length"][:, 2] > 0).all() and (want["pairs"][:, :, 0] < 0).any()   # valid and skipped pairs
+    rot = tc.make("noisy63")["gt"].reshape(-1, 3, 4)[:, :, :3]
+    assert np.abs(rot @ rot.transpose(0, 2, 1) - np.eye(3)).max() > 1e-8      # printed to 7 digits: not orthonormal
+
+
+@pytest.mark.parametrize("name,mode", tc.EVERY)
+def test_host_port_matches_the_reference(port, name, mode):
+    out = tc.host(tc.run(name, mode, port, "cpu"))
+    tc.check(name, mode, out)
+    again = tc.host(tc.run(name, mode, port, "cpu"))
+    assert all(tc.same_bytes(out[k], again[k]) for k in tc.FIELDS)
+    print("worst / bound so far:", {k: round(v, 4) for k, v in tc.WORST.items()})
+
+
+@pytest.mark.parametrize("mode", ref.MODES)
+def test_a_prediction_that_never_moves(port, mode):
+    out = tc.host(tc.run("zero", mode, port, "cpu"))
+    no_scale = mode in ("sim3", "scale")
+    assert np.isnan(out["summary"][6]) == no_scale and np.isnan(out["summary"][[0, 1, 3, 4, 5]]).all() == no_scale
+    assert np.array_equal(out["transform"][:3, :3], np.eye(3)) and not np.isnan(out["aligned"][:, :3, :3]).any()
+    assert np.isnan(out["aligned"][:, :3, 3]).all() == no_scale and np.isfinite(out["traj"]).all()
+    valid = out["pairs"][:, :, 0] >= 0
+    assert valid.any() and np.isnan(out["pairs"][valid][:, 1:3]).all() == no_scale
+    if not no_scale:
+        assert np.isfinite(out["summary"]).all() and out["summary"][6] == 1.0
+
+
+def test_exactly_derived_steps_telescope_to_the_ground_truth(port):
+    """Pins the step convention: with s = 1 and no noise C_j = G^_j, within tau_T plus what the float32 cast of the steps
+    does - every entry of a step moves by at most 2^-24 of its size (<= about 1), a perturbed rotation entry acts on the
+    rest of the path, whose extent is at most max |translation|, and the steps add up linearly: 8 F 2^-24 max(1, max|t|)
+    with the factor tau_T has."""
+    case = tc.make("noisy699")
+    gt, J = case["gt"], case["J"]
+    steps = torch.from_numpy(tc.derive_steps(gt, J, 1.0, 0.0, "general", None))
+    out = tc.host(evaluation.pose_trajectory(steps, gt, align="none", lengths=tc.LENGTHS, step=tc.STEP, backend=port))
+    big = max(1.0, np.abs(out["gt_traj"][:, :3, 3]).max(), np.abs(gt.reshape(-1, 3, 4)[:, :, 3]).max())
+    bound = 8 * (J + 1) * (2.0 ** -52 + 2.0 ** -24) * big
+    worst = np.abs(out["traj"] - out["gt_traj"]).max()
+    print("telescoping: max |C - G^| %.3e (bound %.3e)" % (worst, bound))
+    assert worst <= bound
+    assert np.array_equal(out["aligned"][:, :3], out["traj"][:, :3]) and out["summary"][6] == 1.0     # mode none
+
+
+def test_scale_times_s_is_one_on_the_exact_case(port):
+    out = tc.host(tc.run("exact", "sim3", port, "cpu"))
+    tol = tc.tolerances("exact", "sim3")
+    sigma_g = tc.reference("exact", "sim3")[0]["sigma_g"]
+    s = tc.make("exact")["s"]
+    cast = 8 * 64 * 2.0 ** -24                       # the float32 steps: as in the telescoping test, relative to the path
+    print("c s - 1 = %.3e (bound %.3e)" % (out["summary"][6] * s - 1, tol["tau"] / sigma_g + cast))
+    assert abs(out["summary"][6] * s - 1) <= tol["tau"] / sigma_g + cast
+    assert out["summary"][3] < 1e-4 and out["summary"][0] < 1e-4 and out["summary"][2] > 0
+
+
+@pytest.mark.parametrize("mode", ["sim3", "se3"])
+def test_relative_errors_do_not_see_the_rigid_part_of_the_alignment(port, mode):
+    """t_rel and r_rel depend on the alignment through c alone: multiplying the aligned prediction by ANY rigid
+    transform leaves them where they are.  The entry chains its own trajectory from C_0 = I, so the transform cannot be
+    fed through the steps; it is applied (a) by the reference, to its aligned trajectory before the sub-sequence errors,
+    and (b) by the entry itself: "se3" is "none" times a rigid transform that is far from the identity here."""
+    rng = np.random.default_rng(5)
+    A = tc.rigid(tc.rotation(rng.uniform(-1, 1, 3) * 2), rng.uniform(-50, 50, 3))
+    case = tc.make("noisy63")
+    out = tc.host(tc.run("noisy63", mode, port, "cpu"))
+    moved = ref.evaluate(case["steps"], case["gt"], tc.LENGTHS, tc.STEP, mode, extra=A)
+    tol = tc.tolerances("noisy63", mode)
+    lens = np.asarray(tc.LENGTHS)
+    big = 1 + np.abs(A[:3, 3]).max()                  # the reference's own rounding grows with the size of A
+    tc._within(out["pairs"][:, :, 1] * lens, moved["pairs"][:, :, 1] * lens, 16 * tol["tau"] * big, "t_err L", "moved/" + mode)
+    tc._within(out["pairs"][:, :, 2] * lens, moved["pairs"][:, :, 2] * lens, tol["r"], "r_err L", "moved/" + mode)
+    tc._within(out["summary"][:1] * lens[0], moved["summary"][:1] * lens[0], 16 * tol["tau"] * big, "t_err L", "moved/" + mode)
+    tc._within(out["summary"][1:2] * lens[0], moved["summary"][1:2] * lens[0], tol["r"], "r_err L", "moved/" + mode)
+    if mode == "se3":
+        plain = tc.host(tc.run("noisy63", "none", port, "cpu"))
+        assert np.abs(out["transform"] - np.eye(4)).max() > 1e-4
+        tc._within(out["pairs"][:, :, 1] * lens, plain["pairs"][:, :, 1] * lens, 16 * tol["tau"], "t_err L", "se3 / none")
+        tc._within(out["pairs"][:, :, 2] * lens, plain["pairs"][:, :, 2] * lens, tol["r"], "r_err L", "se3 / none")
+
+
+def test_surplus_ground_truth_rows_are_ignored(port):
+    whole = tc.host(tc.run("surplus", "sim3", port, "cpu"))
+    cut = tc.host(tc.run("surplus", "sim3", port, "cpu", gt_rows=64))
+    assert tc.make("surplus")["gt"].shape[0] == 69 and all(tc.same_bytes(whole[k], cut[k]) for k in tc.FIELDS)
+
+
+def _raw(port, steps, gt, lengths, outs, J, M, n_len, step, mode):
+    lens = (ctypes.c_double * max(len(lengths), 1))(*lengths)
+    return port.dll.hp_pose_trajectory(_lib.ptr(steps), _lib.ptr(gt), ctypes.cast(lens, ctypes.c_void_p),
+                                       *[_lib.ptr(t) for t in outs], J, M, n_len, step, mode)
+
+
+def test_refusals_leave_the_outputs_untouched(port):
+    case = tc.make("noisy63")
+    steps, gt = torch.from_numpy(case["steps"]), torch.from_numpy(case["gt"])
+    outs = [torch.full((64 * 16,), 7.0, dtype=torch.float64) for _ in range(8)]
+    for J, M, lengths, n_len, step, mode in tc.BAD:
+        rc = _raw(port, steps, gt, lengths, outs, J, M, len(lengths) if n_len is None else n_len, step, mode)
+        assert rc == -1, (J, M, lengths, n_len, step, mode, rc)
+    assert _raw(port, steps, gt, tc.LENGTHS, outs, 63, 0x7fffffff // 16 + 1, 4, 4, 0) == -2
+    assert _raw(port, steps, gt, tc.LENGTHS, [None] + outs[1:], 63, 64, 4, 4, 0) == -1
+    assert all(bool((t == 7.0).all()) for t in outs)
+    assert _raw(port, steps, gt, tc.LENGTHS, outs, 63, 64, 4, 4, 0) == 0 and not bool((outs[7][:8] == 7.0).any())
+    # the binding catches the same before it calls
+    for kw in (dict(align="affine"), dict(step=0), dict(lengths=()), dict(lengths=(5.0, 5.0)), dict(lengths=range(1, 10)),
+               dict(lengths=(float("nan"),))):
+        with pytest.raises(ValueError, match="pose_trajectory"):
+            evaluation.pose_trajectory(steps, gt, backend=port, **kw)
+    with pytest.raises(ValueError, match=r"M = 63 < J \+ 1 = 64"):
+        evaluation.pose_trajectory(steps, gt[:63], backend=port)
+    for bad in (steps.double(), steps[:0], steps.view(-1, 8), steps.view(-1, 4, 4)[None]):
+        with pytest.raises(ValueError, match="steps must be float32"):
+            evaluation.pose_trajectory(bad, gt, backend=port)
+    assert evaluation.KITTI_LENGTHS == (100, 200, 300, 400, 500, 600, 700, 800)
+
+
+def test_hip_backend_refuses_cpu_tensors():
+    from baseboostdepth_amd import ops
+    from baseboostdepth_amd.csrc.build import build
+    build()
+    with pytest.raises(_lib.BbdError):
+        tc.run("no_pair", "sim3", ops.HipBackend(), "cpu")
+
+
+def test_options_parse_the_trajectory_flags():
+    o = MonodepthOptions().parse([])
+    assert (o.trajectory, o.trajectory_align, o.save_trajectory) == (False, "sim3", None)
+    o = MonodepthOptions().parse(["--trajectory", "--trajectory_align", "se3", "--save_trajectory", "/tmp/x.txt"])
+    assert (o.trajectory, o.trajectory_align, o.save_trajectory) == (True, "se3", "/tmp/x.txt")
+    for mode in ref.MODES:
+        assert MonodepthOptions().parse(["--trajectory_align", mode]).trajectory_align == mode
+    with pytest.raises(SystemExit):
+        MonodepthOptions().parse(["--trajectory_align", "affine"])
+
+
+# ---------------------------------------------------------------------------- evaluate_pose through the port
+H, W, FRAMES = 8, 16, 40
+
+
+class PassEncoder(torch.nn.Module):
+    num_ch_enc = np.array([6])
+
+    def forward(self, x):
+        return [x]
+
+
+class SpotDecoder(torch.nn.Module):
+    """Stands in for PoseDecoder: a few pixels of the two frames times constants, row by row ([n, 2, 1, 3] twice)."""
+    SPOTS = ((0, 1, 2), (1, 3, 5), (2, 6, 11), (1, 2, 9), (2, 7, 3), (0, 4, 14))
+
+    def forward(self, input_features):
+        x = input_features[0][-1]
+        first = torch.stack([x[:, c, r, col] for c, r, col in self.SPOTS], 1)
+        second = torch.stack([x[:, 3 + c, r, col] for c, r, col in self.SPOTS], 1)
+        diff = second - first
+        axisangle = (diff[:, :3] * 0.05).view(-1, 1, 1, 3)
+        translation = (diff[:, 3:] * 0.2 + torch.tensor([0.0, 0.0, -0.45])).view(-1, 1, 1, 3)
+        return torch.cat([axisangle, axisangle * 0.5], 1), torch.cat([translation, translation * 0.5], 1)
+
+
+def _setup(tmp_path, S, **flags):
+    rng = np.random.default_rng(3)
+    pool = torch.from_numpy(rng.random((FRAMES, 3, H, W)).astype(np.float32))
+    d = tmp_path / "odom" / "sequences" / "09" / "image_2" / "data"
+    os.makedirs(d, exist_ok=True)
+    for t in range(FRAMES):                               # `windows` only asks whether the frames exist
+        open(d / ("%06d.jpg" % t), "wb").close()
+    os.makedirs(tmp_path / "splits" / "odom", exist_ok=True)
+    with open(tmp_path / "splits" / "odom" / "test_files_09.txt", "w") as f:
+        f.write("".join("9 %d l\n" % t for t in range(FRAMES - 1)))
+    gt = tc.make("noisy63")["gt"][:FRAMES]
+    opt = types.SimpleNamespace(eval_split="odom_9", splits_dir=str(tmp_path / "splits"), kt_path=str(tmp_path / "kitti"),
+                                odom_path=None, height=H, width=W, skip_frame=S, track_length=1, cuda=0, num_layers=18,
+                                load_weights_folder="None", num_workers=0, **flags)
+    loader = [{("color", 0, 0): pool[:16]}, {("color", 0, 0): pool[16:]}]
+    return opt, pool, gt, loader
+
+
+def _by_hand(pool, gt, port, align):
+    """One network call per frame pair, then `pose_trajectory` with the devkit's lengths."""
+    from baseboostdepth_amd import ops
+    enc, dec = PassEncoder(), SpotDecoder()
+    with torch.no_grad():
+        steps = []
+        for j in range(FRAMES - 1):
+            axisangle, translation = dec([enc(torch.cat([pool[j:j + 1], pool[j + 1:j + 2]], 1))])
+            steps.append(ops.pose_matrix(axisangle[:, 0], translation[:, 0], backend=port))
+    return evaluation.pose_trajectory(torch.cat(steps), gt, align=align, backend=port)
+
+
+@pytest.mark.parametrize("S", [1, 2, 3])
+def test_evaluate_pose_with_trajectory_equals_the_by_hand_path(port, tmp_path, capsys, S):
+    align = ("sim3", "se3", "scale")[S - 1]
+    opt, pool, gt, loader = _setup(tmp_path, S, trajectory=True, trajectory_align=align,
+                                   save_trajectory=str(tmp_path / "aligned.txt"))
+    port.calls.clear()
+    out = evaluation.evaluate_pose(opt, dataloader=loader, gt_poses=gt, models=(PassEncoder(), SpotDecoder()),
+                                   batch_windows=16, backend=port, device="cpu")
+    said = capsys.readouterr().out
+    assert port.calls.count("bbd_pose_trajectory") == 1 and port.calls.count("bbd_pose_ate") == 1
+    assert port.calls.count("bbd_pose_matrix_fwd") == -(-(FRAMES - S) // 16)          # no further network pass
+    want = tc.host(_by_hand(pool, gt, port, align))
+    assert want["summary"][7] == FRAMES and want["summary"][2] == 0                    # 40 m of path: no 100 m pair
+    assert tc.same_bytes(out["traj_aligned"], want["aligned"]) and tc.same_bytes(out["traj_gt"], want["gt_traj"])
+    assert tc.same_bytes(out["per_length"], want["per_length"]) and out["per_length"].shape == (8, 3)
+    got = np.array([out["t_rel"], out["r_rel"], out["traj_ate_rmse"], out["traj_scale"]])
+    assert tc.same_bytes(got, want["summary"][[0, 1, 3, 6]]) and np.isfinite(got[2:]).all() and np.isnan(got[:2]).all()
+    lines = [l for l in said.splitlines() if l.strip()]
+    assert sum("Trajectory error: " in l for l in lines) == 2 and "Trajectory error: " in lines[-2]
+    assert lines[-1].strip() == "Full trajectory ({}, {:d} frames): t_rel {:0.3f} %, r_rel {:0.3f} deg/100m, ATE {:0.3f} m, " \
+        "scale {:0.4f}".format(align, FRAMES, 100 * got[0], 100 * np.degrees(got[1]), got[2], got[3])
+    saved = evaluation.read_poses_file(str(tmp_path / "aligned.txt"))
+    assert saved.shape == (FRAMES, 12)
+    back = np.array([[float("%.6e" % x) for x in row] for row in want["aligned"].reshape(FRAMES, 16)[:, :12]])
+    assert np.array_equal(saved, back)
+
+
+def test_evaluate_pose_with_real_sub_sequences(port, tmp_path):
+    """The same with ground truth stretched so that the 100 .. 800 m pairs exist: t_rel and r_rel are numbers."""
+    opt, pool, gt, loader = _setup(tmp_path, 2, trajectory=True, trajectory_align="sim3", save_trajectory=None)
+    gt = gt.copy().reshape(-1, 3, 4)
+    gt[:, :, 3] *= 30.0
+    gt = gt.reshape(-1, 12)
+    out = evaluation.evaluate_pose(opt, dataloader=loader, gt_poses=gt, models=(PassEncoder(), SpotDecoder()),
+                                   backend=port, device="cpu")
+    want = tc.host(_by_hand(pool, gt, port, "sim3"))
+    assert want["summary"][2] > 0 and np.isfinite(want["summary"]).all()
+    assert (out["t_rel"], out["r_rel"]) == (want["summary"][0], want["summary"][1])
+    assert tc.same_bytes(out["per_length"], want["per_length"])
+
+
+def test_evaluate_pose_without_the_flag_is_what_it_was(port, tmp_path, capsys):
+    opt, pool, gt, loader = _setup(tmp_path, 2)
+    port.calls.clear()
+    out = evaluation.evaluate_pose(opt, dataloader=loader, gt_poses=gt, models=(PassEncoder(), SpotDecoder()),
+                                   backend=port, device="cpu")
+    said = capsys.readouterr().out
+    assert "bbd_pose_trajectory" not in port.calls
+    assert sorted(out) == sorted(("ate_mean", "ate_std", "ate_chained_mean", "ate_chained_std", "ates", "pred_poses",
+                                  "pred_poses_chained"))
+    assert said == "-> Computing pose predictions\n" \
+        + "\n   Trajectory error: {:0.3f}, std: {:0.3f}\n\n".format(out["ate_mean"], out["ate_std"]) \
+        + "\n   Trajectory error: {:0.3f}, std: {:0.3f}\n\n".format(out["ate_chained_mean"], out["ate_chained_std"])
+    flagged, _, _, loader = _setup(tmp_path, 2, trajectory=True, trajectory_align="sim3", save_trajectory=None)
+    more = evaluation.evaluate_pose(flagged, dataloader=loader, gt_poses=gt, models=(PassEncoder(), SpotDecoder()),
+                                    backend=port, device="cpu")
+    assert capsys.readouterr().out.startswith(said)
+    for k in out:                                          # the flag adds, it changes nothing
+        assert np.array_equal(np.asarray(out[k]), np.asarray(more[k]), equal_nan=True), k
+    with pytest.raises(ValueError, match="--save_trajectory needs --trajectory"):
+        evaluation.evaluate_pose(_setup(tmp_path, 2, save_trajectory="x.txt")[0], gt_poses=gt, backend=port, device="cpu")

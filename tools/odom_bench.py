@@ -7,6 +7,10 @@
         wall time of `evaluation.evaluate_pose` on a synthetic sequence (KITTI-sized JPEGs, 1590 split lines, a poses file)
         at 192 x 640 with ResNet-18 + PoseDecoder on closed-form weights: first call (kernel selection included) and a
         second one
+    python tools/odom_bench.py --trajectory [--out profiles/odom/odom_bench.json]
+        kernel time of one `bbd_pose_trajectory` call (four launches, HIP events around 50 calls after 5 warm-up calls)
+        for J = 1590 steps (sequence 09) and J = 4540 (sequence 00), sim3, the devkit's lengths; the result is added to
+        `--out` under "trajectory"
 """
 import argparse
 import json
@@ -92,10 +96,51 @@ def e2e(frames, out):
             json.dump(result, f, indent=1)
 
 
+def trajectory(out, sizes=(1590, 4540), warmup=5, calls=50):
+    from baseboostdepth_amd import evaluation
+    rows = []
+    for J in sizes:
+        G = np.tile(np.eye(4), (J + 1, 1, 1))
+        for t in range(J + 1):                                    # a wide arc, 0.8 m per frame
+            a = 0.002 * t
+            G[t, :3, :3] = [[math.cos(a), 0, math.sin(a)], [0, 1, 0], [-math.sin(a), 0, math.cos(a)]]
+            G[t, :3, 3] = [400 * (1 - math.cos(a)), 0.01 * math.sin(0.05 * t), 400 * math.sin(a)]
+        rel = np.linalg.inv(G[:-1]) @ G[1:]
+        rel[:, :3, 3] *= 0.5                                      # a monocular network's scale
+        steps = torch.from_numpy(np.linalg.inv(rel).astype(np.float32)).cuda().reshape(J, 16)
+        gt = torch.from_numpy(G[:, :3].reshape(J + 1, 12)).cuda()
+        res = evaluation.pose_trajectory(steps, gt)
+        for _ in range(warmup):
+            evaluation.pose_trajectory_into(steps, gt, evaluation.KITTI_LENGTHS, res, 10, "sim3")
+        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        for _ in range(calls):
+            evaluation.pose_trajectory_into(steps, gt, evaluation.KITTI_LENGTHS, res, 10, "sim3")
+        stop.record()
+        torch.cuda.synchronize()
+        summary = res.summary.cpu().numpy()
+        rows.append({"J": J, "calls": calls, "us_per_call": start.elapsed_time(stop) * 1000.0 / calls,
+                     "t_rel_percent": 100 * float(summary[0]), "pairs": int(summary[2]), "scale": float(summary[6])})
+    result = {"align": "sim3", "lengths": list(evaluation.KITTI_LENGTHS), "step": 10, "timing": "HIP events, host launch "
+              "overhead of 4 launches per call included when it exceeds the kernels", "sizes": rows,
+              "device": torch.cuda.get_device_name(0)}
+    print(json.dumps(result))
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        whole = {}
+        if os.path.isfile(out):
+            with open(out) as f:
+                whole = json.load(f)
+        whole["trajectory"] = result
+        with open(out, "w") as f:
+            json.dump(whole, f, indent=1)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--kernel", action="store_true")
     ap.add_argument("--e2e", action="store_true")
+    ap.add_argument("--trajectory", action="store_true")
     ap.add_argument("--frames", type=int, default=1591)
     ap.add_argument("--out", type=str, default=None)
     args = ap.parse_args()
@@ -104,3 +149,5 @@ if __name__ == "__main__":
         kernel()
     if args.e2e:
         e2e(args.frames, args.out)
+    if args.trajectory:
+        trajectory(args.out)
