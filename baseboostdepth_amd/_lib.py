@@ -20,7 +20,7 @@ PROJ_STRIDE = 24
 KIND_WARP, KIND_IDENT, FLAG_NO_POSE_GRAD = 0, 1, 0x100
 COMPOSE_STRIDE, COMPOSE_ERROR, COMPOSE_REPLACE = 12, 1, 2
 PAIR_SHIFT = 16        # bits 16-23 of bbd_cand_t.kind: 1 + index of the pass partner (hint), 0 = none
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 _p = ctypes.c_void_p
 _i = ctypes.c_int
@@ -72,6 +72,8 @@ SIGNATURES = {
     "bbd_syns_edge_metrics": [_p] * 7 + [_i, _p] + [_i] * 6 + [_d] * 6 + [_i, _p],
     "bbd_chamfer_nn": [_p, _p, _i, _i, _p, _p, _p],
     "bbd_syns_pointcloud": [_p] * 6 + [_i, _p] + [_i] * 6 + [_d] * 5 + [_i, _p],
+    "bbd_point_cloud_scratch_ints": [_i, _i, _i, _i],
+    "bbd_point_cloud": [_p] * 10 + [_i] * 7 + [_d] * 5 + [_i, _p],
     "bbd_pose_ate": [_p] * 6 + [_i] * 4 + [_p],
     "bbd_pose_trajectory": [_p] * 11 + [_i] * 5 + [_p],
     "bbd_post_process_disp": [_p, _p, _i, _i, _i, _p],
@@ -132,6 +134,8 @@ VIZ_DESC = 4
 PANEL_DESC, PANEL_COLOR, PANEL_WARP, PANEL_SCALAR, PANEL_ARGMIN, PANEL_LUT_ROWS = 8, 0, 1, 2, 3, 532
 VELO_DESC, VELO_VEL_DEPTH = 8, 1
 SYNS_OUT, SYNS_CLOUD_OUT, SYNS_RAYS_PIXEL = 8, 8, 8
+CLOUD_DESC, CLOUD_VERTEX = 10, 16                                # BBD_CLOUD_DESC, BBD_CLOUD_VERTEX
+CLOUD_FROM_GT, CLOUD_CLAMP, CLOUD_MASK_GT, CLOUD_RAYS_REFERENCE = 16, 32, 64, 128
 TRAJ_MAX_LEN = 8                                                 # BBD_TRAJ_MAX_LEN
 TRAJ_MODES = {"sim3": 0, "se3": 1, "scale": 2, "none": 3}      # BBD_TRAJ_SIM3 .. BBD_TRAJ_NONE
 EVAL_PRED_IS_DISP, EVAL_MEDIAN_MIDPOINT, EVAL_NO_MEDIAN_SCALING = 1, 2, 4
@@ -216,6 +220,9 @@ class HipLibrary:
 
     def syns_scratch_ints(self, n, px_stride):
         return self._dll.bbd_syns_scratch_ints(n, px_stride)
+
+    def point_cloud_scratch_ints(self, n, max_h, max_w, stride):
+        return self._dll.bbd_point_cloud_scratch_ints(n, max_h, max_w, stride)
 
     def dispconv_scratch_doubles(self, C):
         return self._dll.bbd_dispconv_scratch_doubles(C)

@@ -35,6 +35,7 @@ SRCS = _here("""
     bbd_postproc.hip
     bbd_panel.hip
     bbd_compare.hip
+    bbd_cloud.hip
 """)
 OUT = os.path.join(HERE, "libbbd_hip.so")
 # every header of this directory: one that is forgotten here would leave a stale library behind an edit

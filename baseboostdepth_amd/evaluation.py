@@ -277,7 +277,8 @@ def syns_metrics(pred, gts, indices, inv_K=None, chamfer=False, mode="evaluate",
 STEREO_SCALE_FACTOR = 5.4          # evaluate_depth.py:45
 
 
-def evaluate(opt, dataloader=None, gt_depths=None, models=None, batch_size=16, gt_edges=None, inv_K=None):
+def evaluate(opt, dataloader=None, gt_depths=None, models=None, batch_size=16, gt_edges=None, inv_K=None, backend=None,
+             device=None):
     """KITTI branch of the reference's `evaluate(opt)` (evaluate_depth.py:104-317) for the ResNet and MonoViT (`--ViT`) models:
     predicts disparities for a split, scores them against `gt_depths.npz` with median (mono) or 5.4x
     (stereo) scaling, returns (mean_errors[7], ratios).  Differences by design: images are prepared by the
@@ -304,7 +305,17 @@ def evaluate(opt, dataloader=None, gt_depths=None, models=None, batch_size=16, g
       `ext_disp_to_eval`  path of such a file: its disparities are scored instead of predictions - no weights, no
                           dataset, no loader.  `post_process` and `save_pred_disps` concern predictions and do nothing.
       `no_eval`           stop after the predictions (and the optional save): no ground truth is loaded, nothing is
-                          scored, (None, None) is returned."""
+                          scored, (None, None) is returned.
+
+    `save_clouds` (a directory) writes, for the first `cloud_count` (8) images of the split, the point
+    clouds the evaluation sees as binary PLY files `<index:04d>_pred.ply` and `<index:04d>_gt.ply`, exported by
+    `ops.point_cloud` while the batch is in HBM: the prediction scaled by the ratio of the image's metrics row and
+    clamped to the split's depth range, and the ground truth, both on the pixels the split scores (valid ground truth,
+    inside the Garg window on KITTI), every `cloud_stride`-th of them, coloured by inverse depth.  KITTI takes the KITTI
+    intrinsics at the ground-truth size, SYNS the dataset's; `cloud_rays` ("pixel" | "reference") chooses the pairing of
+    pixels and rays (`pointcloud_metrics`).  It needs the metrics rows, so it is refused together with `no_eval`.
+
+    `backend` and `device` are for tests (the host ports); by default the HIP backend and `cuda:<opt.cuda>`."""
     from . import tuning
     tuning.use_shipped_db()      # (no Trainer is built here: the tuned MIOpen database is wired explicitly)
     import os
@@ -312,16 +323,18 @@ def evaluate(opt, dataloader=None, gt_depths=None, models=None, batch_size=16, g
 
     assert sum((opt.eval_mono, opt.eval_stereo)) == 1, \
         "Please choose mono or stereo evaluation by setting either --eval_mono or --eval_stereo"
-    device = torch.device("cuda:%d" % getattr(opt, "cuda", 0))
+    device = torch.device("cuda:%d" % getattr(opt, "cuda", 0)) if device is None else torch.device(device)
     ext = getattr(opt, "ext_disp_to_eval", None)
     no_eval = bool(getattr(opt, "no_eval", False))
+    clouds = _CloudSaver.from_options(opt, no_eval, backend)             # raises before any prediction
     split_dir = os.path.join(getattr(opt, "splits_dir", "splits"), opt.eval_split)
     syns = opt.eval_split == "SYNS"
 
     def score(source, save_path):
         if syns:
-            return _evaluate_syns(opt, source, save_path, no_eval, gt_depths, gt_edges, inv_K, split_dir, device)
-        return _evaluate_kitti(opt, source, save_path, no_eval, gt_depths, split_dir, device)
+            return _evaluate_syns(opt, source, save_path, no_eval, gt_depths, gt_edges, inv_K, split_dir, device,
+                                  backend, clouds)
+        return _evaluate_kitti(opt, source, save_path, no_eval, gt_depths, split_dir, device, backend, clouds)
 
     if ext is not None:
         return score(_ExternalDisps(ext, batch_size, device), None)
@@ -433,7 +446,57 @@ def _check_count(source, gts):
                          % (source.count, len(gts)))
 
 
-def _evaluate_kitti(opt, source, save_path, no_eval, gt_depths, split_dir, device):
+class _CloudSaver:
+    """`save_clouds`: the prediction and ground-truth clouds of the first `count` images of a split, written as
+    `<index:04d>_pred.ply` / `<index:04d>_gt.ply` batch by batch.  Two `ops.point_cloud` calls and one read-back each
+    per batch that still holds wanted images; nothing at all afterwards."""
+
+    def __init__(self, folder, count, stride, rays, backend):
+        self.folder, self.count, self.stride, self.rays, self.backend = folder, int(count), int(stride), rays, backend
+        self.written = []
+
+    @classmethod
+    def from_options(cls, opt, no_eval, backend):
+        folder = getattr(opt, "save_clouds", None)
+        if folder is None:
+            return None
+        if no_eval:
+            raise ValueError("save_clouds needs the evaluation: the clouds are scaled by the median-scaling ratio of each "
+                             "image's metrics row, and no_eval produces no metrics rows")
+        count, stride = int(getattr(opt, "cloud_count", 8)), int(getattr(opt, "cloud_stride", 1))
+        rays = getattr(opt, "cloud_rays", "pixel")
+        if count < 1 or stride < 1 or rays not in ("pixel", "reference"):
+            raise ValueError("save_clouds: cloud_count and cloud_stride must be at least 1 and cloud_rays pixel or "
+                             "reference, got %r, %r, %r" % (count, stride, rays))
+        return cls(str(folder), count, stride, rays, backend)
+
+    def batch(self, pred_disp, gts, first, rows, inv_K, min_depth, max_depth, scale_factor, median_scaling):
+        """Images first .. first + n - 1 of the split are in `pred_disp`; `rows` are their metrics rows."""
+        import os
+        from . import pointcloud
+        n = min(pred_disp.shape[0], self.count - first)
+        if n <= 0:
+            return
+        os.makedirs(self.folder, exist_ok=True)
+        idx = list(range(first, first + n))
+        desc = gts.desc_host[idx]
+        if inv_K is None:                              # KITTI: the datasets' matrix at every map's own size
+            inv_K = np.stack([pointcloud.intrinsics(*gts.shapes[i]) for i in idx])
+        kw = dict(gt=gts.buffer, stride=self.stride, min_depth=min_depth, max_depth=max_depth, mask_gt=True,
+                  rays=self.rays, backend=self.backend)
+        pred = ops.point_cloud(pred_disp[:n], desc, inv_K, rows=rows[:n].contiguous() if median_scaling else None,
+                               pred_is_disp=True, scale_factor=scale_factor, clamp_depth=True, **kw)
+        truth = ops.point_cloud(pred_disp[:n], desc, inv_K, from_gt=True, **kw)
+        for name, cloud in (("pred", pred), ("gt", truth)):
+            for i, arr in zip(idx, pointcloud.cloud_arrays(*cloud)):
+                self.written.append(pointcloud.write_ply(os.path.join(self.folder, "%04d_%s.ply" % (i, name)), arr))
+
+    def done(self):
+        if self.written:
+            print("-> Saved {:d} point clouds to {}".format(len(self.written), self.folder))
+
+
+def _evaluate_kitti(opt, source, save_path, no_eval, gt_depths, split_dir, device, backend=None, clouds=None):
     """The KITTI splits: every batch of `source` is scored by one `bbd_depth_metrics` launch while it is in HBM."""
     import os
     if no_eval:
@@ -463,10 +526,14 @@ def _evaluate_kitti(opt, source, save_path, no_eval, gt_depths, split_dir, devic
                 kept.append(pred_disp)
             rows.append(depth_metrics(pred_disp, gts, list(range(first, first + n)), min_depth=1e-3, max_depth=80.0,
                                       pred_is_disp=True, median="numpy", median_scaling=median_scaling,
-                                      scale_factor=scale))
+                                      scale_factor=scale, backend=backend))
+            if clouds is not None:
+                clouds.batch(pred_disp, gts, first, rows[-1], None, 1e-3, 80.0, scale, median_scaling)
             first += n
     if save_path is not None:
         _save_disps(kept, save_path)
+    if clouds is not None:
+        clouds.done()
     rows = torch.cat(rows).cpu().numpy().astype(np.float64)          # the only host synchronisation of the scoring
     assert first == len(gts), "split has %d images, ground truth %d" % (first, len(gts))
     mean_errors = rows[:, :7].mean(0)
@@ -479,7 +546,8 @@ def _evaluate_kitti(opt, source, save_path, no_eval, gt_depths, split_dir, devic
     return mean_errors, ratios
 
 
-def _evaluate_syns(opt, source, save_path, no_eval, gt_depths, gt_edges, inv_K, split_dir, device):
+def _evaluate_syns(opt, source, save_path, no_eval, gt_depths, gt_edges, inv_K, split_dir, device, backend=None,
+                   clouds=None):
     """evaluate_depth.py with `--eval_split SYNS [--chamfer]`: every batch is scored while it is in HBM; the rows are
     read back once, at the end."""
     import os
@@ -496,7 +564,7 @@ def _evaluate_syns(opt, source, save_path, no_eval, gt_depths, gt_edges, inv_K, 
                                                                                  edges=gt_edges)
     _check_count(source, gts)
     chamfer = bool(getattr(opt, "chamfer", False))
-    if chamfer and inv_K is None:
+    if (chamfer or clouds is not None) and inv_K is None:
         inv_K = datasets.SYNSRAWDataset.load_intrinsic_syns()[1]
     median_scaling = not opt.disable_median_scaling
     scale = opt.pred_depth_scale_factor
@@ -510,12 +578,17 @@ def _evaluate_syns(opt, source, save_path, no_eval, gt_depths, gt_edges, inv_K, 
                 kept.append(pred_disp)
             res, rows = syns_metrics(pred_disp, gts, list(range(first, first + n)), inv_K=inv_K, chamfer=chamfer,
                                      mode="evaluate", median_scaling=median_scaling, scale_factor=scale,
-                                     return_rows=True)
+                                     return_rows=True, backend=backend)
             out.append(res)
             ratio_rows.append(rows[:, 7])
+            if clouds is not None:
+                # as the clouds of the F-score: without opt.pred_depth_scale_factor (bbd_syns_pointcloud)
+                clouds.batch(pred_disp, gts, first, rows, inv_K, SYNS_MIN_DEPTH, SYNS_MAX_DEPTH, 1.0, median_scaling)
             first += n
     if save_path is not None:
         _save_disps(kept, save_path)
+    if clouds is not None:
+        clouds.done()
     out = torch.cat(out).cpu().numpy()                                  # the only host synchronisation of the scoring
     ratios = torch.cat(ratio_rows).cpu().numpy().astype(np.float64) if median_scaling else None
     assert first == len(gts), "split has %d images, ground truth %d" % (first, len(gts))

@@ -6,6 +6,9 @@ LANCZOS resize + ToTensor kernels (`imageops.ImagePipeline`), the networks, one 
 percentile, normalisation and colour map without leaving the device) and one copy of the colours back; the
 reference does all of that per image on the host with Pillow, numpy and matplotlib (test_simple.py:124-148).
 
+`DepthPredictor.predict_cloud` returns the coloured point cloud of every image instead (`ops.point_cloud`,
+`pointcloud.py`): what `test_simple.py --point_cloud` writes as `<name>_Base.ply`.
+
 `run_cli` is the command line of the repository's root `test_simple.py`.
 """
 import argparse
@@ -16,7 +19,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from . import imageops, ops
+from . import imageops, ops, pointcloud
 
 HOST_THREADS = 8          # decode / save pool; a fixed small number, never the machine's CPU count
 
@@ -145,6 +148,40 @@ class DepthPredictor:
             off += ops.viz_granule(npx)
         return results
 
+    def predict_cloud(self, images, inv_K=None, scale=1.0, max_depth=None, stride=1, post_process=False):
+        """The coloured point cloud of every image: one structured array (`pointcloud.VERTEX_DTYPE`: x, y, z, red,
+        green, blue, alpha) per image, ready for `pointcloud.write_ply`.  The same network pass as `predict`; the
+        scaled disparity min_disp + (max_disp - min_disp) * disp at network size goes through ONE `ops.point_cloud`
+        call, which resamples it at every `stride`-th pixel of the image's own size (as the evaluation resamples a
+        disparity), takes depth = `scale` / disparity (5.4 for stereo-trained weights), back-projects through `inv_K`
+        ([3,3] for all images or one per image; default: the KITTI intrinsics scaled to each image,
+        `pointcloud.intrinsics`) and colours every point with its pixel of the uploaded image.  Points beyond
+        `max_depth` (default: the predictor's `max_depth * scale`) are dropped, as is anything that is not a depth (a
+        negative or non-finite value).  There is no near limit: the sigmoid bounds the disparity."""
+        if not len(images):
+            return []
+        sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
+        if inv_K is None:
+            inv_K = np.stack([pointcloud.intrinsics(H0, W0) for H0, W0 in sizes])
+        far = self.max_depth * scale if max_depth is None else float(max_depth)
+        with torch.no_grad():
+            self.encoder.eval()
+            self.decoder.eval()
+            src, jobs = self.upload(images)
+            x = self.prepare_uploaded(src, jobs)
+            if post_process:
+                disp = ops.post_process_disp(self.disparity(torch.cat((x, torch.flip(x, [3])), 0)), self.backend)
+            else:
+                disp = self.disparity(x)
+            self.last_disp = disp
+            min_disp, max_disp = 1.0 / self.max_depth, 1.0 / self.min_depth
+            scaled = min_disp + (max_disp - min_disp) * disp
+            # `upload` packs the images back to back: image i's bytes start at 3x its pixel offset
+            cloud = ops.point_cloud(scaled, ops.cloud_rows(sizes), inv_K, rgb=src, stride=stride,
+                                    min_depth=0.0, max_depth=far, pred_is_disp=True,
+                                    scale_factor=scale, backend=self.backend)
+            return pointcloud.cloud_arrays(*cloud)
+
 
 def _to_host(t):
     if not t.is_cuda:
@@ -169,9 +206,26 @@ def parse_args(argv=None):
     parser.add_argument("--batch_size", type=int, default=16, help="images per device batch")
     parser.add_argument("--post_process", action="store_true",
                         help="blend the prediction with that of the flipped image (Monodepth2's post-processing)")
+    parser.add_argument("--point_cloud", action="store_true",
+                        help="also write <name>_Base.ply: the coloured point cloud of the prediction (binary PLY)")
+    parser.add_argument("--cloud_scale", type=float, default=1.0,
+                        help="depth = cloud_scale / scaled disparity (5.4 for stereo-trained weights: metres)")
+    parser.add_argument("--cloud_max_depth", type=float, default=None,
+                        help="points beyond this depth are dropped (default: the model's max depth times cloud_scale)")
+    parser.add_argument("--cloud_stride", type=int, default=1, help="export every N-th pixel in both directions")
+    camera = parser.add_mutually_exclusive_group()
+    camera.add_argument("--fov", type=float, default=None, metavar="DEG",
+                        help="horizontal field of view of the camera in degrees (default: the KITTI intrinsics)")
+    camera.add_argument("--intrinsics", type=float, nargs=4, default=None, metavar=("FX", "FY", "CX", "CY"),
+                        help="the camera's intrinsics in pixels of the input image")
     parser.epilog = ("Inputs whose names end in _disp.jpg or _Base.jpg are skipped, so that a second run over a "
                      "folder of jpg files does not colour its own outputs.")
-    return parser.parse_args(argv)
+    args = parser.parse_args(argv)
+    if args.cloud_stride < 1:
+        parser.error("--cloud_stride must be at least 1")
+    if args.cloud_scale <= 0:
+        parser.error("--cloud_scale must be positive")
+    return args
 
 
 def find_inputs(image_path, save_path, ext):
@@ -202,8 +256,20 @@ def _save(out_dir, path, result, save_npy):
     return dest
 
 
+def _save_cloud(out_dir, path, cloud):
+    stem = os.path.splitext(os.path.basename(path))[0]
+    return pointcloud.write_ply(os.path.join(out_dir, "{}_Base.ply".format(stem)), cloud)
+
+
+def _cloud_inv_K(args, images):
+    return np.stack([pointcloud.intrinsics(im.shape[0], im.shape[1], fov=getattr(args, "fov", None),
+                                           fxfycxcy=getattr(args, "intrinsics", None)) for im in images])
+
+
 def run_cli(args, predictor=None):
     """Body of test_simple.py.  `predictor` may be injected (tests); by default it is loaded from `args.weights`.
+    With `--point_cloud` every batch also goes through `predict_cloud` (a second network pass: `predict` is left as it
+    is) and `<name>_Base.ply` is written next to the JPEG.
     Returns the list of written JPEG paths."""
     paths, out_dir = find_inputs(args.image_path, args.save_path, args.ext)
     if predictor is None:
@@ -214,7 +280,7 @@ def run_cli(args, predictor=None):
         os.makedirs(out_dir)
     out_dir = out_dir or "."
     batch = max(1, int(getattr(args, "batch_size", 16)))
-    written, pending = [], []
+    written, pending, cloud_saves = [], [], []
     with ThreadPoolExecutor(max_workers=HOST_THREADS) as pool:
         chunks = [paths[i:i + batch] for i in range(0, len(paths), batch)]
         loads = [pool.map(_load, c) for c in chunks[:1]]                 # decode runs one batch ahead
@@ -227,7 +293,14 @@ def run_cli(args, predictor=None):
             else:
                 results = predictor.predict(images, want_float=args.save_npy)
             pending += [pool.submit(_save, out_dir, p, r, args.save_npy) for p, r in zip(chunk, results)]
+            if getattr(args, "point_cloud", False):
+                clouds = predictor.predict_cloud(images, inv_K=_cloud_inv_K(args, images), scale=args.cloud_scale,
+                                                 max_depth=args.cloud_max_depth, stride=args.cloud_stride,
+                                                 post_process=bool(getattr(args, "post_process", False)))
+                cloud_saves += [pool.submit(_save_cloud, out_dir, p, c) for p, c in zip(chunk, clouds)]
         written = [f.result() for f in pending]
+        for f in cloud_saves:
+            f.result()
     print("-> Done!")
     return written
 

@@ -9,6 +9,7 @@ tests/host_port.py - but nothing in this package can fall back to it.)
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1715,6 +1716,102 @@ def chamfer_nn(a, b, backend=None):
     nn_b = torch.empty(b.shape[0], dtype=torch.float32, device=a.device)
     backend.run("bbd_chamfer_nn", a, ptr(a), ptr(b), a.shape[0], b.shape[0], ptr(nn_a), ptr(nn_b))
     return nn_a, nn_b
+
+
+# ---------------------------------------------------------------------------- coloured point clouds
+def cloud_rows(shapes, offsets=None, windows=None):
+    """Host table int32 [n, 8] of BBD_EVAL_DESC rows for maps of `shapes[i] = (GH, GW)`: element offset (default: the
+    maps lie back to back), size, window `windows[i] = (r0, r1, c0, c1)` (default: the whole image)."""
+    rows, off = np.zeros((len(shapes), _lib.EVAL_DESC), dtype=np.int32), 0
+    for i, (gh, gw) in enumerate(shapes):
+        o = off if offsets is None else int(offsets[i])
+        rows[i] = split64(o) + (int(gh), int(gw)) + (tuple(int(v) for v in windows[i]) if windows is not None
+                                                       else (0, int(gh), 0, int(gw)))
+        off += int(gh) * int(gw)
+    return rows
+
+
+def cloud_capacity(row, stride):
+    """Candidate pixels of one descriptor row at `stride`: every stride-th pixel of the window (cut to the image) in
+    both directions, starting at its first."""
+    gh, gw, r0, r1, c0, c1 = (int(v) for v in row[2:8])
+    r0, r1, c0, c1 = max(r0, 0), min(r1, gh), max(c0, 0), min(c1, gw)
+    if gh < 1 or gw < 1 or r1 <= r0 or c1 <= c0:
+        return 0
+    return ((r1 - r0 - 1) // stride + 1) * ((c1 - c0 - 1) // stride + 1)
+
+
+def point_cloud(pred, rows_desc, inv_K, gt=None, rows=None, rgb=None, stride=1, min_depth=1e-3, max_depth=80.0,
+                clamp=(1e-3, 80.0), pred_is_disp=False, scale_factor=1.0, from_gt=False, clamp_depth=False,
+                mask_gt=False, rays="pixel", out=None, regions=None, backend=None):
+    """The coloured point clouds of a ragged batch in ONE `bbd_point_cloud` call (three launches, nothing read back):
+    `pred` ([n,1,h,w] or [n,h,w], depth or - `pred_is_disp` - disparity) is resampled at every `stride`-th pixel of the
+    window of image i as `evaluation.depth_metrics` resamples it, multiplied by `rows[i][7]` (that call's output; None:
+    1), back-projected through `inv_K` ([3,3], [4,4] or one per image) along the pixel's own ray (`rays="pixel"`) or
+    the reference's pairing (`rays="reference"`), and coloured from `rgb` (uint8 device buffer, image i as HWC at 3x its
+    element offset) or, without it, magma over inverse depth.  Points outside [min_depth, max_depth] are dropped -
+    clamped with `clamp_depth`; `mask_gt` keeps only pixels with min_depth < gt < max_depth; `from_gt` exports the
+    ground truth `gt` (float32 device buffer at the offsets of `rows_desc`) instead of the prediction.
+
+    `rows_desc` is a host table of BBD_EVAL_DESC rows (`cloud_rows`, or `GroundTruthSet.desc_host[indices]`).  Image
+    i's region starts at vertex `regions[i]` of `out` (uint8, 16 bytes per vertex); by default the regions follow one
+    another at their capacities in a new buffer.  Returns (vertices, counts, offsets): the device buffer, int32 [n] on
+    the device, and the regions' first vertices (host ints).  `pointcloud.cloud_arrays` brings them to the host."""
+    backend = backend or default_backend()
+    assert rays in ("pixel", "reference")
+    pred = pred.detach()
+    if pred.dim() == 4:
+        assert pred.shape[1] == 1
+        pred = pred[:, 0]
+    pred = pred.contiguous().float()
+    n, h, w = pred.shape
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError("point_cloud: stride must be at least 1, got %r" % (stride,))
+    if (from_gt or mask_gt) and gt is None:
+        raise ValueError("point_cloud: from_gt and mask_gt read the ground truth, which was not given")
+    desc8 = np.asarray(rows_desc, dtype=np.int64).reshape(-1, _lib.EVAL_DESC)
+    assert desc8.shape[0] == n and n > 0
+    dev = pred.device
+    caps = [cloud_capacity(r, stride) for r in desc8]
+    if regions is None:
+        assert out is None
+        regions = [0] * n
+        for i in range(1, n):
+            regions[i] = regions[i - 1] + caps[i - 1]
+        out = torch.empty((regions[-1] + caps[-1]) * _lib.CLOUD_VERTEX, dtype=torch.uint8, device=dev)
+    regions = [int(r) for r in regions]
+    assert out is not None and out.dtype == torch.uint8 and out.dim() == 1 and out.is_contiguous()
+    assert len(regions) == n and all(r >= 0 and (r + c) * _lib.CLOUD_VERTEX <= out.numel() for r, c in zip(regions, caps))
+    table = np.zeros((n, _lib.CLOUD_DESC), dtype=np.int32)
+    table[:, :_lib.EVAL_DESC] = desc8
+    table[:, _lib.EVAL_DESC:] = [split64(r) for r in regions]
+    iK = torch.as_tensor(np.asarray(inv_K, dtype=np.float32))
+    iK = iK[..., :3, :3].expand(n, 3, 3) if iK.dim() == 2 else iK[:, :3, :3]
+    assert tuple(iK.shape) == (n, 3, 3)
+    iK = upload(iK.contiguous(), dev)
+    if rows is not None:
+        assert rows.dtype == torch.float32 and tuple(rows.shape) == (n, _lib.EVAL_OUT) and rows.is_contiguous()
+    if rgb is not None:
+        assert rgb.dtype == torch.uint8 and rgb.dim() == 1 and rgb.is_contiguous()
+    if gt is not None:
+        assert gt.dtype == torch.float32 and gt.dim() == 1 and gt.is_contiguous()
+    backend._check(pred, gt, rows, rgb, out)
+    max_h, max_w = int(desc8[:, 2].max()), int(desc8[:, 3].max())
+    n_ints = backend.lib.point_cloud_scratch_ints(n, max_h, max_w, stride)
+    if n_ints < 0:
+        raise _lib.BbdError("point_cloud: %d images of up to %d x %d pixels are more than one call holds; split the batch"
+                            % (n, max_h, max_w))
+    desc = upload(table, dev)
+    counts = torch.empty(n, dtype=torch.int32, device=dev)
+    scratch = torch.empty(n_ints, dtype=torch.int32, device=dev)
+    flags = (_lib.EVAL_PRED_IS_DISP if pred_is_disp else 0) | (_lib.CLOUD_FROM_GT if from_gt else 0) | \
+            (_lib.CLOUD_CLAMP if clamp_depth else 0) | (_lib.CLOUD_MASK_GT if mask_gt else 0) | \
+            (_lib.CLOUD_RAYS_REFERENCE if rays == "reference" else 0)
+    backend.run("bbd_point_cloud", pred, ptr(pred), ptr(gt), ptr(desc), ptr(rows), ptr(iK), ptr(rgb),
+                ptr(magma_lut(dev)), ptr(out), ptr(counts), ptr(scratch), n_ints, n, h, w, max_h, max_w, stride,
+                float(min_depth), float(max_depth), float(clamp[0]), float(clamp[1]), float(scale_factor), flags)
+    return out, counts, regions
 
 
 # ---------------------------------------------------------------------------- flip post-processing

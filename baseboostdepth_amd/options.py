@@ -62,6 +62,11 @@ _FLAGS = [
     # panels = text + pictures rendered on the device (target, disparity, minimum-loss map, arg-min map, the warps)
     ("--train_log", dict(type=str, default="off", choices=["off", "text", "panels"])),
     ("--log_samples", dict(type=int, default=1)),
+    # evaluate_depth.py: write the clouds of the first --cloud_count images of the split, prediction and ground truth, as
+    # <index>_pred.ply / <index>_gt.ply into this directory while the batch is in HBM
+    ("--save_clouds", dict(type=str, default=None, metavar="DIR")), ("--cloud_count", dict(type=int, default=8)),
+    ("--cloud_stride", dict(type=int, default=1)),
+    ("--cloud_rays", dict(type=str, default="pixel", choices=["pixel", "reference"])),
 ]
 # other zoos / datasets of the reference: parsed, refused when set
 _OUT_OF_SCOPE = ["--SYNS_eval", "--SQL", "--SQL_L", "--CA_depth", "--DIFFNet", "--stereo_guide",
@@ -99,6 +104,12 @@ class MonodepthOptions:
         bad = [f for f in _OUT_OF_SCOPE if getattr(self.options, f[2:])]
         if bad:
             self.parser.error("%s select parts of the reference that are outside this build's scope" % ", ".join(bad))
+        if self.options.save_clouds is not None:
+            if self.options.no_eval:
+                self.parser.error("--save_clouds needs the evaluation: the clouds are scaled by the median-scaling ratio "
+                                  "of each image's metrics row, and --no_eval produces no metrics rows")
+            if self.options.cloud_count < 1 or self.options.cloud_stride < 1:
+                self.parser.error("--cloud_count and --cloud_stride must be at least 1")
         if self.options.rand and not self.options.no_step_graph:
             self.options.step_graph = True
         if self.options.early_pose_rows != "max":

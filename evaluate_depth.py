@@ -2,6 +2,9 @@
 """Depth evaluation with the reference's command line:
 
     python evaluate_depth.py --eval_mono --load_weights_folder <weights> --kt_path <kitti> --eval_split eigen
+
+`--save_clouds DIR [--cloud_count N] [--cloud_stride N] [--cloud_rays pixel|reference]` also writes the point clouds of
+the first N images, prediction and ground truth, as binary PLY files.
 """
 from baseboostdepth_amd.evaluation import evaluate
 from baseboostdepth_amd.options import MonodepthOptions

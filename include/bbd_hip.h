@@ -40,7 +40,7 @@ extern "C" {
  * 11 = bbd_pose_ate (KITTI odometry evaluation: chained poses, local ground truth, trajectory error);
  * 12 = bbd_post_process_disp (depth evaluation: flip post-processing of the predicted disparities);
  * 14 = bbd_pose_trajectory (KITTI odometry: full-trajectory t_rel, r_rel and aligned ATE). */
-#define BBD_ABI_VERSION 14
+#define BBD_ABI_VERSION 15
 
 /* Source frames live in separate tensors, one per frame id (inputs[("color", f, 0)],
  * trainer.py:428).  A "slot" indexes a host array of their base pointers. */
@@ -477,6 +477,55 @@ int bbd_syns_pointcloud(const float* pred, const float* gt, const int32_t* desc,
                         const float* inv_K, int32_t* scratch, int scratch_ints, float* out, int n, int h, int w,
                         int px_stride, int max_h, int max_w, double min_depth, double max_depth, double clamp_lo,
                         double clamp_hi, double th, int flags, void* stream);
+
+/* ---- Coloured point clouds (csrc/bbd_cloud.hip, pointcloud.py): the cloud of a prediction, or of its
+ * ground truth, for a ragged batch of n images per call, compacted on the device into vertices of BBD_CLOUD_VERTEX =
+ * 16 bytes - x, y, z float32 little-endian, then red, green, blue, alpha - the vertex record of a binary PLY file.
+ *   pred    float32 [n,h,w], depth or (BBD_EVAL_PRED_IS_DISP) disparity, resampled at every exported pixel by
+ *           bbd_eval_resample exactly as bbd_depth_metrics does it (clamp_lo / clamp_hi, scale_factor as there)
+ *   gt      float32 ragged buffer at the desc offsets; may be NULL unless a flag below reads it
+ *   desc[i] = {offset_lo, offset_hi, GH, GW, r0, r1, c0, c1, out_lo, out_hi}            (BBD_CLOUD_DESC int32)
+ *           the BBD_EVAL_DESC row of the image, then the position, in vertices, of the image's region in `vertices`.
+ *           [r0,r1) x [c0,c1) is the window of pixels to export (whole image = 0,GH,0,GW; it is cut to the image)
+ *   rows    float32 [n, BBD_EVAL_OUT] of bbd_depth_metrics, read on the device: rows[i][7] is the median-scaling ratio;
+ *           NULL = ratio 1
+ *   inv_K   float32 [n,3,3] row-major
+ *   rgb     uint8 RGB images of GH x GW at rgb + 3 * offset, or NULL
+ *   lut     uint8 [256,3], magma (baseboostdepth_amd/magma_lut.hex); may be NULL where rgb is given
+ * The CANDIDATES of image i are the pixels (y, x) of the window with (y - r0) % stride == 0 and (x - c0) % stride == 0,
+ * in raster order; their number is the capacity of the region, which the caller provides.  For a candidate:
+ *   d = rows[i][7] * bbd_eval_resample(...)  (the order bbd_syns_pointcloud forms pred_org in), or, with
+ *       BBD_CLOUD_FROM_GT, d = gt at the pixel
+ *   kept when d is finite and min_depth <= d <= max_depth: a zero disparity gives inf and is dropped, NaN is dropped
+ *       BBD_CLOUD_CLAMP    d is clamped to [min_depth, max_depth] instead (NaN is still dropped)
+ *       BBD_CLOUD_MASK_GT  additionally min_depth < gt < max_depth at the pixel: the pixels the F-score scores
+ *   xyz = bbd_syns_backproject(inv_K[i], k = y * GW + x, GH, GW, pixel_rays, d): the pixel's own ray (k % GW, k / GW),
+ *       or with BBD_CLOUD_RAYS_REFERENCE the reference's pairing (k / GH, k % GH)
+ *   rgb = the pixel's three bytes, or lut[idx] from inverse depth in float32: t = (1/d - 1/max_depth) /
+ *       (1/min_depth - 1/max_depth), idx = min(max((int)(t * 256), 0), 255); alpha = 255
+ * (operation by operation: csrc/bbd_cloud_math.h, -ffp-contract=off).  The kept vertices of image i are written from
+ * the start of its region, contiguously, in the raster order of their pixels, each with one aligned 16-byte store;
+ * counts[i] (int32) is their number.  Bytes of a region past 16 * counts[i] and bytes outside all regions are not
+ * written.  `vertices` is 16-byte aligned.
+ * max_h / max_w >= every GH / GW of the batch: they size the launches and the scratch, bbd_point_cloud_scratch_ints(n,
+ * max_h, max_w, stride) int32 that need no initialisation; an image larger than that exports nothing (counts[i] = 0).
+ * Three launches - kept candidates per chunk of 256 (64-bit ballot, population count), a prefix sum of every image's
+ * chunk totals, the write pass - no atomics, no allocation, no host synchronisation; integer sums only, so nothing
+ * depends on launch geometry and identical calls give identical bytes.
+ * A NULL required pointer, n, h, w, max_h, max_w or stride below 1, an unknown flag bit, a flag that reads gt with gt
+ * NULL, vertices not 16-byte aligned or scratch_ints too small return BBD_E_BADARG; n > 65535, max_h * max_w >
+ * 2^31 - 257 or a scratch size beyond int32 return BBD_E_TOOMANY.  Nothing is launched then. */
+#define BBD_CLOUD_DESC 10
+#define BBD_CLOUD_VERTEX 16
+#define BBD_CLOUD_FROM_GT 16
+#define BBD_CLOUD_CLAMP 32
+#define BBD_CLOUD_MASK_GT 64
+#define BBD_CLOUD_RAYS_REFERENCE 128
+int bbd_point_cloud_scratch_ints(int n, int max_h, int max_w, int stride);
+int bbd_point_cloud(const float* pred, const float* gt, const int32_t* desc, const float* rows, const float* inv_K,
+                    const uint8_t* rgb, const uint8_t* lut, void* vertices, int32_t* counts, int32_t* scratch,
+                    int scratch_ints, int n, int h, int w, int max_h, int max_w, int stride, double min_depth,
+                    double max_depth, double clamp_lo, double clamp_hi, double scale_factor, int flags, void* stream);
 
 /* Flip post-processing of predicted disparities (Monodepth2's batch_post_process_disparity; evaluate_depth.py
  * --post_process), n images per call.
