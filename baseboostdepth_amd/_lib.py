@@ -20,7 +20,7 @@ PROJ_STRIDE = 24
 KIND_WARP, KIND_IDENT, FLAG_NO_POSE_GRAD = 0, 1, 0x100
 COMPOSE_STRIDE, COMPOSE_ERROR, COMPOSE_REPLACE = 12, 1, 2
 PAIR_SHIFT = 16        # bits 16-23 of bbd_cand_t.kind: 1 + index of the pass partner (hint), 0 = none
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 _p = ctypes.c_void_p
 _i = ctypes.c_int
@@ -74,6 +74,11 @@ SIGNATURES = {
     "bbd_syns_pointcloud": [_p] * 6 + [_i, _p] + [_i] * 6 + [_d] * 5 + [_i, _p],
     "bbd_point_cloud_scratch_ints": [_i, _i, _i, _i],
     "bbd_point_cloud": [_p] * 10 + [_i] * 7 + [_d] * 5 + [_i, _p],
+    "bbd_map_state_bytes": [_i],
+    "bbd_map_finish_scratch_ints": [_i],
+    "bbd_map_clear": [_p] * 4 + [_i, _p],
+    "bbd_map_accumulate": [_p] * 4 + [_i] + [_p] * 5 + [_i] * 8 + [_d] * 3 + [_i, _p],
+    "bbd_map_finish": [_p] * 3 + [_i, _i, _d] + [_p] * 5 + [_i, _p],
     "bbd_pose_ate": [_p] * 6 + [_i] * 4 + [_p],
     "bbd_pose_trajectory": [_p] * 11 + [_i] * 5 + [_p],
     "bbd_post_process_disp": [_p, _p, _i, _i, _i, _p],
@@ -135,6 +140,7 @@ PANEL_DESC, PANEL_COLOR, PANEL_WARP, PANEL_SCALAR, PANEL_ARGMIN, PANEL_LUT_ROWS 
 VELO_DESC, VELO_VEL_DEPTH = 8, 1
 SYNS_OUT, SYNS_CLOUD_OUT, SYNS_RAYS_PIXEL = 8, 8, 8
 CLOUD_DESC, CLOUD_VERTEX = 10, 16                                # BBD_CLOUD_DESC, BBD_CLOUD_VERTEX
+MAP_INPUT_IS_DEPTH, MAP_NO_MERGE, MAP_COUNTERS, MAP_SLOT_BYTES, MAP_MAX_T = 1, 2, 4, 48, 1 << 30   # BBD_MAP_*
 CLOUD_FROM_GT, CLOUD_CLAMP, CLOUD_MASK_GT, CLOUD_RAYS_REFERENCE = 16, 32, 64, 128
 TRAJ_MAX_LEN = 8                                                 # BBD_TRAJ_MAX_LEN
 TRAJ_MODES = {"sim3": 0, "se3": 1, "scale": 2, "none": 3}      # BBD_TRAJ_SIM3 .. BBD_TRAJ_NONE
@@ -159,7 +165,7 @@ class HipLibrary:
         for name, argtypes in SIGNATURES.items():
             fn = getattr(self._dll, name)   # AttributeError here = header/library mismatch
             fn.argtypes = argtypes
-            fn.restype = ctypes.c_long if name.endswith("_scratch_floats") else _i
+            fn.restype = ctypes.c_long if name.endswith(("_scratch_floats", "_state_bytes")) else _i
         if self._dll.bbd_abi_version() != ABI_VERSION:
             raise BbdError("libbbd_hip.so ABI version mismatch")
         self.smooth_chunks = self._dll.bbd_smooth_chunks()
@@ -223,6 +229,12 @@ class HipLibrary:
 
     def point_cloud_scratch_ints(self, n, max_h, max_w, stride):
         return self._dll.bbd_point_cloud_scratch_ints(n, max_h, max_w, stride)
+
+    def map_state_bytes(self, T):
+        return self._dll.bbd_map_state_bytes(T)
+
+    def map_finish_scratch_ints(self, T):
+        return self._dll.bbd_map_finish_scratch_ints(T)
 
     def dispconv_scratch_doubles(self, C):
         return self._dll.bbd_dispconv_scratch_doubles(C)

@@ -19,11 +19,13 @@
 // or on scheduling, and there are no atomics.  The depth is evaluated twice rather than kept between the passes: it
 // costs four reads of a prediction that sits in cache, keeping it would cost 4 B written and read per candidate.
 // No allocation, no host synchronisation; the chunk table is the caller's scratch and needs no initialisation.
+// The ballots, the scan and the slot of a kept lane are bbd_compact.h, which bbd_map.hip shares.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/bbd_hip.h"
 #include "bbd_cloud_math.h"
+#include "bbd_compact.h"
 #include "bbd_device_util.h"
 
 namespace {
@@ -44,7 +46,7 @@ struct CloudCall {
 
 __global__ __launch_bounds__(CT) void cloud_count_kernel(CloudCall a) {
   __shared__ int wave_kept[CW];
-  const int img = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int img = blockIdx.y, tid = threadIdx.x;
   const BbdCloudImg m = bbd_cloud_img(a.p.desc, img, a.p.stride, a.p.max_h, a.p.max_w);
   const int n_chunks = (m.cap + CT - 1) / CT;                      // <= chunk_stride: cap <= the largest grid
   int32_t* table = a.chunks + (size_t)img * a.chunk_stride;
@@ -53,48 +55,23 @@ __global__ __launch_bounds__(CT) void cloud_count_kernel(CloudCall a) {
     int pixel;
     float d;
     const bool keep = c < m.cap && bbd_cloud_depth(&a.p, &m, img, c, &pixel, &d);
-    const unsigned long long mask = __ballot(keep);
-    if (lane == 0) wave_kept[wave] = __popcll(mask);
+    compact_ballot(keep, wave_kept);
     __syncthreads();
-    if (tid == 0) {
-      int s = 0;
-      for (int wv = 0; wv < CW; ++wv) s += wave_kept[wv];
-      table[chunk] = s;
-    }
+    if (tid == 0) table[chunk] = compact_total<CW>(wave_kept);
     __syncthreads();
   }
 }
 
 __global__ __launch_bounds__(ST) void cloud_scan_kernel(CloudCall a) {
   __shared__ int wave_total[SW];
-  const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int img = blockIdx.x;
   const BbdCloudImg m = bbd_cloud_img(a.p.desc, img, a.p.stride, a.p.max_h, a.p.max_w);
-  const int n_chunks = (m.cap + CT - 1) / CT;
-  int32_t* table = a.chunks + (size_t)img * a.chunk_stride;
-  const int run = (n_chunks + ST - 1) / ST, j0 = min(tid * run, n_chunks), j1 = min(j0 + run, n_chunks);
-  int s = 0;
-  for (int j = j0; j < j1; ++j) s += table[j];
-  int incl = s;
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
-  if (lane == 63) wave_total[wave] = incl;
-  __syncthreads();
-  int before = 0;
-  for (int wv = 0; wv < wave; ++wv) before += wave_total[wv];
-  int prefix = before + incl - s;                                    // kept candidates before this lane's run
-  for (int j = j0; j < j1; ++j) {
-    const int t = table[j];
-    table[j] = prefix;
-    prefix += t;
-  }
-  if (tid == ST - 1) a.counts[img] = before + incl;
+  compact_scan<ST>(a.chunks + (size_t)img * a.chunk_stride, (m.cap + CT - 1) / CT, wave_total, a.counts + img);
 }
 
 __global__ __launch_bounds__(CT) void cloud_write_kernel(CloudCall a) {
   __shared__ int wave_kept[CW];
-  const int img = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int img = blockIdx.y, tid = threadIdx.x;
   const BbdCloudImg m = bbd_cloud_img(a.p.desc, img, a.p.stride, a.p.max_h, a.p.max_w);
   const int n_chunks = (m.cap + CT - 1) / CT;
   const int32_t* table = a.chunks + (size_t)img * a.chunk_stride;
@@ -104,13 +81,10 @@ __global__ __launch_bounds__(CT) void cloud_write_kernel(CloudCall a) {
     int pixel = 0;
     float d = 0.0f;
     const bool keep = c < m.cap && bbd_cloud_depth(&a.p, &m, img, c, &pixel, &d);
-    const unsigned long long mask = __ballot(keep);
-    if (lane == 0) wave_kept[wave] = __popcll(mask);
+    const unsigned long long mask = compact_ballot(keep, wave_kept);
     __syncthreads();
     if (keep) {
-      int slot = table[chunk];
-      for (int wv = 0; wv < wave; ++wv) slot += wave_kept[wv];
-      slot += __popcll(mask & ((1ull << lane) - 1ull));              // kept lanes below this one; slot < counts[i] <= cap
+      const int slot = compact_slot(table[chunk], mask, wave_kept);  // < counts[i] <= cap
       uint32_t v[4];
       bbd_cloud_vertex(&a.p, &m, img, pixel, d, v);
       out[slot] = make_uint4(v[0], v[1], v[2], v[3]);

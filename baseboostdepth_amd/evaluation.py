@@ -789,6 +789,12 @@ def evaluate_pose(opt, dataloader=None, gt_poses=None, models=None, batch_window
     in %, r_rel in deg / 100 m, the ATE rmse in metres, the scale) and the dict gains `t_rel` (a fraction), `r_rel`
     (rad / m), `traj_ate_rmse`, `traj_scale`, `per_length` ([8, 3]: mean t_err, mean r_err, count for 100 .. 800 m),
     `traj_aligned` and `traj_gt` ([F,4,4]).  `opt.save_trajectory` writes the aligned poses as a KITTI poses file.
+
+    `opt.save_map` (needs `opt.trajectory`) writes the scene map of the sequence as a binary PLY file (`_scene_map`,
+    DESIGN.md 6j): the depth network (`encoder.pth` / `depth.pth` of the same folder, `opt.ViT` honoured, or `models[2:4]`)
+    runs over every `opt.map_every`-th frame of the pool, and each batch goes into a `pointcloud.SceneMap` with its rows
+    of the aligned trajectory and the alignment's scale, both still on the device.  One more line is printed and the dict
+    gains `map_stats` (frames, candidates, kept, dropped_range, dropped_full, voxels) and `map_path`.
     `backend` / `device` are the seam of the test tier (default: the HIP backend on `cuda:<opt.cuda>`)."""
     import os
     from . import datasets, networks, tuning
@@ -801,6 +807,10 @@ def evaluate_pose(opt, dataloader=None, gt_poses=None, models=None, batch_window
     align = getattr(opt, "trajectory_align", "sim3")
     if save_trajectory and not trajectory:
         raise ValueError("evaluate_pose: --save_trajectory needs --trajectory")
+    save_map = getattr(opt, "save_map", None)
+    if save_map and not trajectory:
+        raise ValueError("evaluate_pose: --save_map needs --trajectory")
+    map_opt = _map_options(opt) if save_map else None
     if trajectory and align not in TRAJ_MODES:
         raise ValueError("evaluate_pose: --trajectory_align must be one of %s, got %r" % (", ".join(TRAJ_MODES), align))
     # ---- host: the window tables and the ground truth, checked before anything is launched
@@ -822,9 +832,10 @@ def evaluate_pose(opt, dataloader=None, gt_poses=None, models=None, batch_window
         decoder = networks.PoseDecoder(encoder.num_ch_enc, 1, 2)
         decoder.load_state_dict(torch.load(os.path.join(folder, "pose.pth"), map_location=device))
     else:
-        encoder, decoder = models
+        encoder, decoder = models[:2]
     encoder.to(device).eval()
     decoder.to(device).eval()
+    predictor = _map_predictor(opt, models, height, width, device, backend) if save_map else None
     if dataloader is None:
         pool_set = datasets.KITTIOdomDataset(frames, 0, height, width, kt_path=opt.kt_path, is_train=False, kt=True,
                                              naive_mix=True, odom_path=odom_root)
@@ -884,4 +895,68 @@ def evaluate_pose(opt, dataloader=None, gt_poses=None, models=None, batch_window
                       out["traj_scale"]))
         if save_trajectory:
             np.savetxt(save_trajectory, both[0].reshape(frames_scored, 16)[:, :12], fmt="%.6e")
+        if save_map:
+            if F != frames_scored:
+                raise ValueError("evaluate_pose: --save_map needs the frames of one side of one sequence: the pool holds "
+                                 "%d frames, the trajectory %d" % (F, frames_scored))
+            out["map_stats"] = _scene_map(predictor, pool, tr, map_opt, save_map, backend)
+            out["map_path"] = save_map
+            print("   Scene map: {frames:d} frames, {candidates:d} candidates, {kept:d} kept, {voxels:d} voxels -> {}\n"
+                  .format(save_map, **out["map_stats"]))
     return out
+
+
+def _map_options(opt):
+    """The --map_* options of `opt` with their defaults, checked."""
+    m = {"voxel": float(getattr(opt, "map_voxel", 0.2)), "every": int(getattr(opt, "map_every", 1)),
+         "stride": int(getattr(opt, "map_stride", 2)), "min_depth": float(getattr(opt, "map_min_depth", 0.5)),
+         "max_depth": float(getattr(opt, "map_max_depth", 30.0)), "min_points": int(getattr(opt, "map_min_points", 1)),
+         "capacity": int(getattr(opt, "map_capacity", 1 << 24))}
+    if not (m["voxel"] > 0.0 and np.isfinite(m["voxel"])):
+        raise ValueError("evaluate_pose: --map_voxel must be positive, got %r" % m["voxel"])
+    if min(m["every"], m["stride"], m["min_points"], m["capacity"]) < 1:
+        raise ValueError("evaluate_pose: --map_every, --map_stride, --map_min_points and --map_capacity must be at least 1")
+    if not m["min_depth"] <= m["max_depth"]:
+        raise ValueError("evaluate_pose: --map_min_depth %r exceeds --map_max_depth %r" % (m["min_depth"], m["max_depth"]))
+    return m
+
+
+def _map_predictor(opt, models, height, width, device, backend):
+    """The depth network of --save_map: `models[2:4]` where a depth pair was injected, else the weights folder's."""
+    import os
+    from .inference import DepthPredictor
+    kw = dict(min_depth=getattr(opt, "min_depth", 0.1), max_depth=getattr(opt, "max_depth", 100.0), backend=backend)
+    if models is not None and len(models) >= 4:
+        return DepthPredictor(models[2], models[3], height, width, device, **kw)
+    folder = os.path.expanduser(opt.load_weights_folder)
+    predictor = DepthPredictor.from_weights(folder, vit=bool(getattr(opt, "ViT", False)),
+                                            num_layers=getattr(opt, "num_layers", 18), device=device, **kw)
+    if (predictor.feed_height, predictor.feed_width) != (height, width):
+        raise ValueError("evaluate_pose: --save_map feeds the depth network the frames of the pose evaluation, %d x %d, "
+                         "but %s was trained at %d x %d; pass --height %d --width %d"
+                         % (height, width, folder, predictor.feed_height, predictor.feed_width, predictor.feed_height,
+                            predictor.feed_width))
+    return predictor
+
+
+def _scene_map(predictor, pool, tr, m, path, backend=None):
+    """The scene map of a sequence: every `every`-th frame of `pool` [F,3,H,W] through the depth network in batches, each
+    batch straight into `SceneMap.add` with its rows of `tr.aligned` and the scale `tr.summary[6:7]` (1 under se3 / none)
+    - nothing is read back before `finish`.  Writes `path`; returns the statistics."""
+    from . import pointcloud
+    F, _, H, W = pool.shape
+    scene = pointcloud.SceneMap(m["voxel"], m["capacity"], pool.device, backend)
+    inv_K = upload(pointcloud.intrinsics(H, W), pool.device)
+    min_disp, max_disp = 1.0 / predictor.max_depth, 1.0 / predictor.min_depth
+    rows = list(range(0, F, m["every"]))
+    with torch.no_grad():
+        for lo in range(0, len(rows), predictor.batch_size):
+            sel = slice(rows[lo], rows[min(lo + predictor.batch_size, len(rows)) - 1] + 1, m["every"])
+            rgb = pool[sel].contiguous()
+            disp = min_disp + (max_disp - min_disp) * predictor.disparity(rgb)
+            scene.add(disp, rgb, tr.aligned[sel].contiguous(), inv_K, scale=tr.summary[6:7], stride=m["stride"],
+                      min_depth=m["min_depth"], max_depth=m["max_depth"])
+        vertices, _, stats = scene.finish(m["min_points"])
+    pointcloud.write_ply(path, vertices)
+    stats["frames"] = len(rows)
+    return stats

@@ -6,6 +6,7 @@ product has: it refuses non-GPU tensors and raises if the extension is missing. 
 tier injects a host build of the same arithmetic through the `backend=` seam - see
 tests/host_port.py - but nothing in this package can fall back to it.)
 """
+import collections
 import ctypes
 import os
 
@@ -1812,6 +1813,113 @@ def point_cloud(pred, rows_desc, inv_K, gt=None, rows=None, rgb=None, stride=1, 
                 ptr(magma_lut(dev)), ptr(out), ptr(counts), ptr(scratch), n_ints, n, h, w, max_h, max_w, stride,
                 float(min_depth), float(max_depth), float(clamp[0]), float(clamp[1]), float(scale_factor), flags)
     return out, counts, regions
+
+
+# ---------------------------------------------------------------------------- scene map (voxel fusion)
+MapState = collections.namedtuple("MapState", "keys pos col counters T")
+MapState.__doc__ = """The caller-owned state of the `bbd_map_*` entries for a table of T slots: `keys` int64 [T] (the
+uint64 voxel keys, empty = -1), `pos` int64 [T,3], `col` int32 [T,4] (sum r, g, b, count), `counters` int64 [4]
+(candidates, kept, out-of-range drops, table-full drops)."""
+
+
+def map_state(capacity, device, backend=None):
+    """A cleared `MapState` of `capacity` slots rounded up to a power of two."""
+    backend = backend or default_backend()
+    capacity = int(capacity)
+    if capacity < 1 or capacity > _lib.MAP_MAX_T:
+        raise ValueError("map_state: the capacity must lie in [1, 2^30] slots, got %d" % capacity)
+    T = 1 << (capacity - 1).bit_length()
+    assert backend.lib.map_state_bytes(T) == T * _lib.MAP_SLOT_BYTES + 8 * _lib.MAP_COUNTERS
+    state = MapState(torch.empty(T, dtype=torch.int64, device=device), torch.empty(T, 3, dtype=torch.int64, device=device),
+                     torch.empty(T, 4, dtype=torch.int32, device=device),
+                     torch.empty(_lib.MAP_COUNTERS, dtype=torch.int64, device=device), T)
+    map_clear(state, backend)
+    return state
+
+
+def _map_state_ptrs(state, backend):
+    keys, pos, col, counters, T = state
+    assert keys.dtype == torch.int64 and pos.dtype == torch.int64 and col.dtype == torch.int32
+    assert counters.dtype == torch.int64 and counters.numel() == _lib.MAP_COUNTERS
+    assert keys.numel() == T and pos.numel() == 3 * T and col.numel() == 4 * T
+    backend._check(keys, pos, col, counters)
+    return ptr(keys), ptr(pos), ptr(col), ptr(counters), int(T)
+
+
+def map_clear(state, backend=None):
+    """`bbd_map_clear`: every slot empty, sums and counters zero (one launch)."""
+    backend = backend or default_backend()
+    backend.run("bbd_map_clear", state.keys, *_map_state_ptrs(state, backend))
+
+
+def map_accumulate(state, disp, rgb, poses, inv_K, scale=None, stride=1, window=None, min_depth=0.5, max_depth=30.0,
+                   voxel=0.2, is_depth=False, merge=True, backend=None):
+    """`bbd_map_accumulate` (one launch, nothing read back): the points of n frames go into the voxel table.  `disp`
+    float32 [n,h,w] or [n,1,h,w], the scaled disparity (or, `is_depth`, depth); `rgb` float32 [n,3,h,w] in [0,1];
+    `poses` float64 [n,4,4] or [n,16] camera to world; `inv_K` float32 [3,3] (host or device); `scale` None or a
+    float64 DEVICE tensor of one element that multiplies depths and points (`PoseTrajectory.summary[6:7]`);
+    `window` = (r0, r1, c0, c1), default the whole image; every `stride`-th pixel of it is a candidate; the depth
+    limits are in world units.  `merge=False` selects the form that adds every point for itself (BBD_MAP_NO_MERGE: the
+    same state byte for byte, kept for measurements and tests)."""
+    backend = backend or default_backend()
+    disp = disp.detach()
+    if disp.dim() == 4:
+        assert disp.shape[1] == 1
+        disp = disp[:, 0]
+    if disp.dim() != 3 or disp.dtype != torch.float32:
+        raise ValueError("map_accumulate: disp must be float32 [n,h,w] or [n,1,h,w], got %s %s"
+                         % (disp.dtype, tuple(disp.shape)))
+    n, h, w = disp.shape
+    rgb, poses = rgb.detach(), poses.detach()
+    if rgb.dtype != torch.float32 or tuple(rgb.shape) != (n, 3, h, w):
+        raise ValueError("map_accumulate: rgb must be float32 [%d,3,%d,%d], got %s %s"
+                         % (n, h, w, rgb.dtype, tuple(rgb.shape)))
+    if poses.dtype != torch.float64 or poses.numel() != 16 * n or poses.shape[0] != n:
+        raise ValueError("map_accumulate: poses must be float64 [%d,4,4], got %s %s" % (n, poses.dtype, tuple(poses.shape)))
+    stride = int(stride)
+    if n < 1 or stride < 1:
+        raise ValueError("map_accumulate: at least one frame and a stride of at least 1 are needed")
+    if not (float(voxel) > 0.0 and np.isfinite(float(voxel))):
+        raise ValueError("map_accumulate: the voxel size must be positive and finite, got %r" % (voxel,))
+    if not float(min_depth) <= float(max_depth):
+        raise ValueError("map_accumulate: min_depth %r exceeds max_depth %r" % (min_depth, max_depth))
+    r0, r1, c0, c1 = (0, h, 0, w) if window is None else (int(v) for v in window)
+    dev = disp.device
+    disp, rgb, poses = disp.contiguous(), rgb.contiguous(), poses.contiguous()
+    iK = inv_K if torch.is_tensor(inv_K) else torch.as_tensor(np.asarray(inv_K, dtype=np.float32))
+    assert iK.dtype == torch.float32 and tuple(iK.shape) == (3, 3)
+    iK = upload(iK.contiguous(), dev) if iK.device != dev else iK.contiguous()
+    if scale is not None:
+        assert scale.dtype == torch.float64 and scale.numel() == 1 and scale.device == dev
+    backend._check(disp, rgb, poses, iK, scale)
+    sp = _map_state_ptrs(state, backend)
+    # `scale` may be a view into a larger tensor: its address is taken as it is
+    backend.run("bbd_map_accumulate", disp, *sp, ptr(disp), ptr(rgb), ptr(poses), ptr(iK),
+                ctypes.c_void_p(0 if scale is None else scale.data_ptr()), n, h, w, r0, r1, c0, c1, stride,
+                float(min_depth), float(max_depth), float(voxel),
+                (_lib.MAP_INPUT_IS_DEPTH if is_depth else 0) | (0 if merge else _lib.MAP_NO_MERGE))
+
+
+def map_finish(state, voxel, min_points=1, backend=None):
+    """`bbd_map_finish` (three launches, nothing read back): the occupied slots with at least `min_points` points, in
+    slot order.  Returns (out_keys int64 [T], vertices uint8 [16 T], out_counts int32 [T], m int32 [1]) on the device;
+    the first m records are written.  The state is only read."""
+    backend = backend or default_backend()
+    min_points = int(min_points)
+    if min_points < 1:
+        raise ValueError("map_finish: min_points must be at least 1, got %d" % min_points)
+    keys_p, pos_p, col_p, _, T = _map_state_ptrs(state, backend)
+    dev = state.keys.device
+    n_ints = backend.lib.map_finish_scratch_ints(T)
+    assert n_ints >= 1
+    out_keys = torch.empty(T, dtype=torch.int64, device=dev)
+    vertices = torch.empty(T * _lib.CLOUD_VERTEX, dtype=torch.uint8, device=dev)
+    out_counts = torch.empty(T, dtype=torch.int32, device=dev)
+    m = torch.empty(1, dtype=torch.int32, device=dev)
+    scratch = torch.empty(n_ints, dtype=torch.int32, device=dev)
+    backend.run("bbd_map_finish", state.keys, keys_p, pos_p, col_p, T, min_points, float(voxel), ptr(out_keys),
+                ptr(vertices), ptr(out_counts), ptr(m), ptr(scratch), n_ints)
+    return out_keys, vertices, out_counts, m
 
 
 # ---------------------------------------------------------------------------- flip post-processing

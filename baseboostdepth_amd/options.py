@@ -98,6 +98,18 @@ class MonodepthOptions:
                                  help="alignment of the predicted trajectory to ground truth before it is scored")
         self.parser.add_argument("--save_trajectory", type=str, default=None,
                                  help="with --trajectory: write the aligned poses to this file, 12 numbers per row")
+        # the scene map of the sequence: depth predictions placed by the aligned trajectory, fused on a voxel grid
+        # (DESIGN.md 6j); the depth limits are in the units of the aligned trajectory (metres under sim3)
+        self.parser.add_argument("--save_map", type=str, default=None, metavar="FILE.ply",
+                                 help="with --trajectory: write the voxel-fused coloured point cloud of the sequence")
+        self.parser.add_argument("--map_voxel", type=float, default=0.2, help="edge of a voxel")
+        self.parser.add_argument("--map_every", type=int, default=1, help="use every k-th frame")
+        self.parser.add_argument("--map_stride", type=int, default=2, help="use every k-th pixel of a frame, both ways")
+        self.parser.add_argument("--map_min_depth", type=float, default=0.5)
+        self.parser.add_argument("--map_max_depth", type=float, default=30.0)
+        self.parser.add_argument("--map_min_points", type=int, default=1, help="drop voxels with fewer points")
+        self.parser.add_argument("--map_capacity", type=int, default=1 << 24,
+                                 help="slots of the voxel table (rounded up to a power of two, 48 bytes each)")
 
     def parse(self, argv=None):
         self.options = self.parser.parse_args(argv)

@@ -4,6 +4,9 @@
 red, green, blue, alpha - which is exactly the vertex record the PLY header below declares.  `cloud_arrays` copies the
 whole buffer to pinned host memory once and hands out numpy views of it; `write_ply` writes the header and then those
 bytes as they came from the device.  Nothing here touches a point.
+
+`SceneMap` fuses the clouds of many posed frames on a voxel grid (`ops.map_*`) and reads the finished
+voxels back once, as one array of the same vertex record.
 """
 import numpy as np
 import torch
@@ -117,3 +120,76 @@ def read_ply(path):
     if len(body) != count * CLOUD_VERTEX:
         raise ValueError("read_ply: %s declares %d vertices but holds %d bytes of them" % (path, count, len(body)))
     return np.frombuffer(body, dtype=VERTEX_DTYPE).copy()
+
+
+class SceneMap:
+    """A scene map: the points of posed frames fused on a grid of `voxel`-sized cells, one coloured vertex per occupied
+    cell (`bbd_map_*`).  The state - an open-addressing hash table of `capacity` slots, rounded up to a
+    power of two, 48 bytes each - lives on `device`; `add` launches one kernel per batch and reads nothing back."""
+
+    DEFAULT_CAPACITY = 1 << 24
+    CAPACITY_FLAG = "--map_capacity"
+
+    def __init__(self, voxel=0.2, capacity=None, device="cuda:0", backend=None):
+        from . import ops
+        self.voxel = float(voxel)
+        if not (self.voxel > 0.0 and np.isfinite(self.voxel)):
+            raise ValueError("SceneMap: the voxel size must be positive and finite, got %r" % (voxel,))
+        self.backend = backend or ops.default_backend()
+        self.device = torch.device(device)
+        self.state = ops.map_state(self.DEFAULT_CAPACITY if capacity is None else capacity, self.device, self.backend)
+        self.capacity = self.state.T
+        self.scale, self.offered = None, 0
+
+    def clear(self):
+        from . import ops
+        ops.map_clear(self.state, self.backend)
+        self.scale, self.offered = None, 0
+
+    def add(self, disp, rgb, poses, inv_K, scale=None, stride=1, window=None, min_depth=0.5, max_depth=30.0,
+            is_depth=False, merge=True):
+        """One `ops.map_accumulate` call: see there.  `scale` is a float64 device tensor of one element, or None."""
+        from . import ops
+        ops.map_accumulate(self.state, disp, rgb, poses, inv_K, scale=scale, stride=stride, window=window,
+                           min_depth=min_depth, max_depth=max_depth, voxel=self.voxel, is_depth=is_depth,
+                           merge=merge, backend=self.backend)
+        self.scale = scale if scale is not None else self.scale          # the last one given: read back by finish
+        self.offered += int(disp.shape[0]) * int(disp.shape[-2]) * int(disp.shape[-1])    # no more voxels than pixels
+
+    def finish(self, min_points=1):
+        """The voxels with at least `min_points` points, in ascending key order (keys are unique: the order does not
+        depend on how the table filled).  ONE pinned read-back.  Returns (vertices as `VERTEX_DTYPE`, counts int32 [M],
+        stats = dict(candidates, kept, dropped_range, dropped_full, voxels)).  Raises when the table overflowed, and when
+        nothing was kept because the `scale` is NaN."""
+        from . import ops
+        out_keys, vertices, out_counts, m = ops.map_finish(self.state, self.voxel, min_points, self.backend)
+        T = self.capacity
+        R = max(1, min(T, self.offered))                   # records that can have been written: all that is read back
+        # plumbing: order by key.  Records past m take the largest key, so they sort behind the written ones.
+        valid = torch.arange(T, device=out_keys.device) < m.to(torch.int64)
+        order = torch.sort(torch.where(valid, out_keys, torch.full_like(out_keys, torch.iinfo(torch.int64).max))).indices[:R]
+        words = vertices.view(torch.int32).view(T, 4)[order]
+        packed = torch.cat([words.reshape(-1), out_counts[order], m, self.state.counters.view(torch.int32)]
+                           + ([] if self.scale is None else [self.scale.reshape(1).view(torch.int32)])).contiguous()
+        if packed.is_cuda:
+            host = torch.empty(packed.shape, dtype=packed.dtype, pin_memory=True)
+            host.copy_(packed, non_blocking=True)
+            torch.cuda.current_stream(packed.device).synchronize()
+        else:
+            host = packed
+        flat = host.numpy()
+        M = int(flat[5 * R])
+        counters = flat[5 * R + 1:5 * R + 9].copy().view(np.int64)
+        scale = 1.0 if self.scale is None else float(flat[5 * R + 9:].copy().view(np.float64)[0])
+        stats = {"candidates": int(counters[0]), "kept": int(counters[1]), "dropped_range": int(counters[2]),
+                 "dropped_full": int(counters[3]), "voxels": M}
+        if stats["dropped_full"] > 0:
+            raise RuntimeError("SceneMap: the voxel table of %d slots is full, %d points found no slot; raise the "
+                               "capacity (%s)" % (T, stats["dropped_full"], self.CAPACITY_FLAG))
+        if np.isnan(scale) and stats["kept"] == 0:
+            raise RuntimeError("SceneMap: the scale is NaN, so none of the %d candidate points was kept; a prediction "
+                               "that never moves has no sim3 scale (--trajectory_align se3 needs none)"
+                               % stats["candidates"])
+        assert M <= R
+        verts = flat[:4 * M].copy().view(np.uint8).view(VERTEX_DTYPE)
+        return verts, flat[4 * R:4 * R + M].copy(), stats

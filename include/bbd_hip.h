@@ -39,8 +39,9 @@ extern "C" {
  * 10 = bbd_syns_* / bbd_chamfer_nn (SYNS-Patches evaluation: edge and point-cloud metrics);
  * 11 = bbd_pose_ate (KITTI odometry evaluation: chained poses, local ground truth, trajectory error);
  * 12 = bbd_post_process_disp (depth evaluation: flip post-processing of the predicted disparities);
- * 14 = bbd_pose_trajectory (KITTI odometry: full-trajectory t_rel, r_rel and aligned ATE). */
-#define BBD_ABI_VERSION 15
+ * 14 = bbd_pose_trajectory (KITTI odometry: full-trajectory t_rel, r_rel and aligned ATE);
+ * 15 = bbd_point_cloud (coloured point clouds); 16 = bbd_map_* (voxel-fused scene map). */
+#define BBD_ABI_VERSION 16
 
 /* Source frames live in separate tensors, one per frame id (inputs[("color", f, 0)],
  * trainer.py:428).  A "slot" indexes a host array of their base pointers. */
@@ -526,6 +527,73 @@ int bbd_point_cloud(const float* pred, const float* gt, const int32_t* desc, con
                     const uint8_t* rgb, const uint8_t* lut, void* vertices, int32_t* counts, int32_t* scratch,
                     int scratch_ints, int n, int h, int w, int max_h, int max_w, int stride, double min_depth,
                     double max_depth, double clamp_lo, double clamp_hi, double scale_factor, int flags, void* stream);
+
+/* ---- Scene map (csrc/bbd_map.hip, pointcloud.SceneMap): the points of many frames, each placed in the
+ * world by its camera-to-world pose, fused on a voxel grid into one coloured cloud.  A streaming accumulator: the state
+ * is the caller's, an open-addressing hash table of T slots, T a power of two up to 2^30:
+ *   keys      uint64 [T]     voxel key of the slot, empty = all ones
+ *   pos       uint64 [T,3]   sums of the points' fixed-point offsets inside the voxel (16 fractional bits), x y z
+ *   col       uint32 [T,4]   sum of red, green, blue bytes, number of points; 16-byte aligned
+ *   counters  int64 [BBD_MAP_COUNTERS] = {candidates, kept, out-of-range drops, table-full drops}, running totals
+ * bbd_map_state_bytes(T) = T * BBD_MAP_SLOT_BYTES + 8 * BBD_MAP_COUNTERS, the bytes of the four buffers together.
+ *
+ * bbd_map_clear: every key empty, sums and counters zero.  One launch.
+ *
+ * bbd_map_accumulate adds n frames.  One launch, a lane per candidate.
+ *   disp    float32 [n,h,w]: the network's scaled disparity (depth = 1 / disp), or, with BBD_MAP_INPUT_IS_DEPTH, depth
+ *   rgb     float32 [n,3,h,w] in [0,1]
+ *   poses   float64 [n,16] row-major 4x4, camera to world
+ *   inv_K   float32 [3,3] row-major
+ *   scale   DEVICE pointer to one double that multiplies depth and camera-frame point (bbd_pose_trajectory's
+ *           summary + 6), or NULL = 1
+ *   [r0,r1) x [c0,c1) is the window of pixels (it is cut to the image); the CANDIDATES are its pixels (y, x) with
+ *   (y - r0) % stride == 0 and (x - c0) % stride == 0.  For a candidate, k = y * w + x:
+ *     d = 1.0f / disp (or disp), float32;  x = bbd_syns_backproject(inv_K, k, h, w, pixel rays, d), float32
+ *     dm = scale * (double)d: the candidate is REJECTED unless dm is finite and min_depth <= dm <= max_depth (the limits
+ *       are in world units; a zero or NaN disparity and a NaN scale are rejected here)
+ *     X = R (scale * (double)x) + t in float64, three-term sums left to right
+ *     per axis u = X / voxel, v = floor(u), q = (uint32)((u - v) * 65536.0); a non-finite X or |v| >= 2^20 on any axis:
+ *       the point is dropped and counted OUT OF RANGE
+ *     key = ((v_x + 2^20) << 42) | ((v_y + 2^20) << 21) | (v_z + 2^20)
+ *     colour byte = min(max((int)(c * 255.0f + 0.5f), 0), 255) per channel
+ *   (operation by operation: csrc/bbd_map_math.h, -ffp-contract=off).  The point's slot is found by linear probing from
+ *   mix(key) & (T - 1) - mix = splitmix64's finaliser: z ^= z >> 30, z *= 0xbf58476d1ce4e5b9, z ^= z >> 27,
+ *   z *= 0x94d049bb133111eb, z ^= z >> 31 - with a 64-bit compare-and-swap on keys; at most T slots are visited, a point
+ *   that finds none is dropped and counted TABLE FULL.  On the slot q_x q_y q_z are added to pos and r, g, b, 1 to col
+ *   with integer atomic adds: the sums do not depend on the order of arrival, the slot a key occupies does.
+ *   Neighbouring candidates of a wave that fall into one voxel are summed in registers first and added once; with
+ *   BBD_MAP_NO_MERGE every point adds for itself.  The state's bytes are the same either way (profiles/map/README.md).
+ *   counters: candidates += n * candidates per frame, kept += points added, and the two drop counts.
+ *   A voxel takes fewer than 2^24 points (the colour sums are 32 bits).
+ *
+ * bbd_map_finish compacts the occupied slots with count >= min_points, in slot order, into
+ *   out_keys  int64 [T]: the voxel keys (below 2^63), so that the caller can order the voxels; keys are unique
+ *   vertices  [T] records of BBD_CLOUD_VERTEX bytes, 16-byte aligned: per axis
+ *             (float)((v + ((double)sum_q / count + 0.5) / 65536.0) * voxel), per channel (sum + count / 2) / count in
+ *             integers, alpha 255
+ *   out_counts int32 [T]; m int32 [1]: the number of records M.  Records past M are not written.
+ *   scratch   int32 [bbd_map_finish_scratch_ints(T)], no initialisation
+ * Three launches, the compaction of bbd_point_cloud (csrc/bbd_compact.h).  The state is only read: accumulation may go
+ * on afterwards.  `voxel` is the one the points were accumulated with.
+ *
+ * No allocation, no host synchronisation.  A NULL required pointer, T, n, h, w, stride or min_points below 1, T not a
+ * power of two, voxel not positive and finite, min_depth > max_depth (or a NaN limit), col or vertices not 16-byte
+ * aligned, scratch_ints too small or an unknown flag bit return BBD_E_BADARG; T > 2^30 or n * h * w > INT_MAX return
+ * BBD_E_TOOMANY.  Nothing is launched then.  The size helpers return the same codes. */
+#define BBD_MAP_INPUT_IS_DEPTH 1
+#define BBD_MAP_NO_MERGE 2
+#define BBD_MAP_COUNTERS 4
+#define BBD_MAP_SLOT_BYTES 48
+long bbd_map_state_bytes(int T);
+int bbd_map_finish_scratch_ints(int T);
+int bbd_map_clear(uint64_t* keys, uint64_t* pos, uint32_t* col, int64_t* counters, int T, void* stream);
+int bbd_map_accumulate(uint64_t* keys, uint64_t* pos, uint32_t* col, int64_t* counters, int T, const float* disp,
+                       const float* rgb, const double* poses, const float* inv_K, const double* scale, int n, int h,
+                       int w, int r0, int r1, int c0, int c1, int stride, double min_depth, double max_depth,
+                       double voxel, int flags, void* stream);
+int bbd_map_finish(const uint64_t* keys, const uint64_t* pos, const uint32_t* col, int T, int min_points, double voxel,
+                   int64_t* out_keys, void* vertices, int32_t* out_counts, int32_t* m, int32_t* scratch,
+                   int scratch_ints, void* stream);
 
 /* Flip post-processing of predicted disparities (Monodepth2's batch_post_process_disparity; evaluate_depth.py
  * --post_process), n images per call.
