@@ -20,7 +20,7 @@ PROJ_STRIDE = 24
 KIND_WARP, KIND_IDENT, FLAG_NO_POSE_GRAD = 0, 1, 0x100
 COMPOSE_STRIDE, COMPOSE_ERROR, COMPOSE_REPLACE = 12, 1, 2
 PAIR_SHIFT = 16        # bits 16-23 of bbd_cand_t.kind: 1 + index of the pass partner (hint), 0 = none
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 _p = ctypes.c_void_p
 _i = ctypes.c_int
@@ -79,6 +79,10 @@ SIGNATURES = {
     "bbd_map_clear": [_p] * 4 + [_i, _p],
     "bbd_map_accumulate": [_p] * 4 + [_i] + [_p] * 5 + [_i] * 8 + [_d] * 3 + [_i, _p],
     "bbd_map_finish": [_p] * 3 + [_i, _i, _d] + [_p] * 5 + [_i, _p],
+    "bbd_view_clear": [_p, _p, _i, _i, _p],
+    "bbd_view_points": [_p, _p, _i, _i, _p, _p, _i, _p, _i, _p],
+    "bbd_view_lines": [_p, _p, _i, _i, _p, _i, _p, _i, _d, _i, _i, _p],
+    "bbd_view_resolve": [_p, _i, _i, _i, _p, _p],
     "bbd_pose_ate": [_p] * 6 + [_i] * 4 + [_p],
     "bbd_pose_trajectory": [_p] * 11 + [_i] * 5 + [_p],
     "bbd_post_process_disp": [_p, _p, _i, _i, _i, _p],
@@ -141,6 +145,7 @@ VELO_DESC, VELO_VEL_DEPTH = 8, 1
 SYNS_OUT, SYNS_CLOUD_OUT, SYNS_RAYS_PIXEL = 8, 8, 8
 CLOUD_DESC, CLOUD_VERTEX = 10, 16                                # BBD_CLOUD_DESC, BBD_CLOUD_VERTEX
 MAP_INPUT_IS_DEPTH, MAP_NO_MERGE, MAP_COUNTERS, MAP_SLOT_BYTES, MAP_MAX_T = 1, 2, 4, 48, 1 << 30   # BBD_MAP_*
+VIEW_COUNTERS, VIEW_MAX_CELLS, VIEW_MAX_LAYER = 4, 1 << 28, 65535                                   # BBD_VIEW_*
 CLOUD_FROM_GT, CLOUD_CLAMP, CLOUD_MASK_GT, CLOUD_RAYS_REFERENCE = 16, 32, 64, 128
 TRAJ_MAX_LEN = 8                                                 # BBD_TRAJ_MAX_LEN
 TRAJ_MODES = {"sim3": 0, "se3": 1, "scale": 2, "none": 3}      # BBD_TRAJ_SIM3 .. BBD_TRAJ_NONE

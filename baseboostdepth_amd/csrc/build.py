@@ -37,6 +37,7 @@ SRCS = _here("""
     bbd_compare.hip
     bbd_cloud.hip
     bbd_map.hip
+    bbd_view.hip
 """)
 OUT = os.path.join(HERE, "libbbd_hip.so")
 # every header of this directory: one that is forgotten here would leave a stale library behind an edit

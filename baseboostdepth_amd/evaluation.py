@@ -795,6 +795,12 @@ def evaluate_pose(opt, dataloader=None, gt_poses=None, models=None, batch_window
     runs over every `opt.map_every`-th frame of the pool, and each batch goes into a `pointcloud.SceneMap` with its rows
     of the aligned trajectory and the alignment's scale, both still on the device.  One more line is printed and the dict
     gains `map_stats` (frames, candidates, kept, dropped_range, dropped_full, voxels) and `map_path`.
+
+    `opt.save_plot` (needs `opt.trajectory`) writes a picture of the run (`_trajectory_plot`): the ground
+    truth and the aligned prediction seen from above (`opt.plot_view`: or from the side), over the map's voxels where
+    `opt.save_map` is given, with a disc at the start and a scale bar.  It is drawn on the device from what is already
+    there and read back once.  One more line is printed and the dict gains `plot_stats` (view, m_per_px, scale_bar and
+    the voxels offered, drawn, clipped, rejected) and `plot_path`.
     `backend` / `device` are the seam of the test tier (default: the HIP backend on `cuda:<opt.cuda>`)."""
     import os
     from . import datasets, networks, tuning
@@ -811,6 +817,10 @@ def evaluate_pose(opt, dataloader=None, gt_poses=None, models=None, batch_window
     if save_map and not trajectory:
         raise ValueError("evaluate_pose: --save_map needs --trajectory")
     map_opt = _map_options(opt) if save_map else None
+    save_plot = getattr(opt, "save_plot", None)
+    if save_plot and not trajectory:
+        raise ValueError("evaluate_pose: --save_plot needs --trajectory")
+    plot_opt = _plot_options(opt) if save_plot else None
     if trajectory and align not in TRAJ_MODES:
         raise ValueError("evaluate_pose: --trajectory_align must be one of %s, got %r" % (", ".join(TRAJ_MODES), align))
     # ---- host: the window tables and the ground truth, checked before anything is launched
@@ -899,10 +909,16 @@ def evaluate_pose(opt, dataloader=None, gt_poses=None, models=None, batch_window
             if F != frames_scored:
                 raise ValueError("evaluate_pose: --save_map needs the frames of one side of one sequence: the pool holds "
                                  "%d frames, the trajectory %d" % (F, frames_scored))
-            out["map_stats"] = _scene_map(predictor, pool, tr, map_opt, save_map, backend)
+            out["map_stats"], scene = _scene_map(predictor, pool, tr, map_opt, save_map, backend)
             out["map_path"] = save_map
             print("   Scene map: {frames:d} frames, {candidates:d} candidates, {kept:d} kept, {voxels:d} voxels -> {}\n"
                   .format(save_map, **out["map_stats"]))
+        if save_plot:
+            out["plot_stats"] = _trajectory_plot(tr, both, scene if save_map else None, map_opt, plot_opt, save_plot,
+                                                 device, backend)
+            out["plot_path"] = save_plot
+            print("   Plot: {view}, {m_per_px:.4g} m/px, scale bar {scale_bar:g} m, {drawn:d} of {offered:d} voxels -> {}\n"
+                  .format(save_plot, **out["plot_stats"]))
     return out
 
 
@@ -942,7 +958,7 @@ def _map_predictor(opt, models, height, width, device, backend):
 def _scene_map(predictor, pool, tr, m, path, backend=None):
     """The scene map of a sequence: every `every`-th frame of `pool` [F,3,H,W] through the depth network in batches, each
     batch straight into `SceneMap.add` with its rows of `tr.aligned` and the scale `tr.summary[6:7]` (1 under se3 / none)
-    - nothing is read back before `finish`.  Writes `path`; returns the statistics."""
+    - nothing is read back before `finish`.  Writes `path`; returns the statistics and the map."""
     from . import pointcloud
     F, _, H, W = pool.shape
     scene = pointcloud.SceneMap(m["voxel"], m["capacity"], pool.device, backend)
@@ -959,4 +975,84 @@ def _scene_map(predictor, pool, tr, m, path, backend=None):
         vertices, _, stats = scene.finish(m["min_points"])
     pointcloud.write_ply(path, vertices)
     stats["frames"] = len(rows)
+    return stats, scene
+
+
+PLOT_GT, PLOT_PRED, PLOT_START, PLOT_BAR = (40, 40, 40), (214, 39, 40), (31, 119, 180), (0, 0, 0)
+
+
+def _plot_options(opt):
+    """The --plot_* options of `opt` with their defaults, checked."""
+    p = {"view": getattr(opt, "plot_view", "top"), "size": int(getattr(opt, "plot_size", 1024)),
+         "ceiling": float(getattr(opt, "plot_ceiling", 3.0)), "point_size": int(getattr(opt, "plot_point_size", 1))}
+    if p["view"] not in ("top", "side"):
+        raise ValueError("evaluate_pose: --plot_view is top or side, got %r" % (p["view"],))
+    if not 16 <= p["size"] <= 16384:
+        raise ValueError("evaluate_pose: --plot_size must lie in [16, 16384], got %d" % p["size"])
+    if p["point_size"] not in (1, 3, 5, 7):
+        raise ValueError("evaluate_pose: --plot_point_size is 1, 3, 5 or 7, got %d" % p["point_size"])
+    if not (p["ceiling"] > 0.0 and np.isfinite(p["ceiling"])):     # the cameras themselves must stay below the near plane
+        raise ValueError("evaluate_pose: --plot_ceiling must be positive and finite, got %r" % p["ceiling"])
+    return p
+
+
+def scale_bar_length(metres):
+    """The largest of 1, 2, 5 x 10^k that is <= `metres` (> 0)."""
+    k = int(np.floor(np.log10(metres)))
+    best = None
+    for e in (k - 1, k, k + 1):
+        for m in (1.0, 2.0, 5.0):
+            c = m * 10.0 ** e
+            if c <= metres and (best is None or c > best):
+                best = c
+    return best
+
+
+def plot_layout(both, p):
+    """What `--save_plot` draws besides the two trajectories, from the host copy `both` [2,F,4,4] (aligned prediction,
+    ground truth): the view and its metres per pixel, the scale bar's length and its two world positions."""
+    from . import pointcloud
+    pos = np.ascontiguousarray(both[:, :, :3, 3], dtype=np.float64).reshape(-1, 3)
+    if not np.isfinite(pos).all():
+        raise ValueError("evaluate_pose: --save_plot needs finite trajectories (a prediction that never moves has no sim3 "
+                         "scale; --trajectory_align se3 needs none)")
+    lo, hi = pos.min(0), pos.max(0)
+    size = p["size"]
+    # top: y points down, so the highest camera has the smallest y; what lies more than the ceiling above it is clipped
+    near = lo[1] - p["ceiling"] if p["view"] == "top" else None
+    view, mpp = pointcloud.ortho_view(lo, hi, size, size, plane=p["view"], near=near)
+    bar = scale_bar_length(0.25 * size * mpp)
+    # the bar: lower left, 4 % of the picture in from both edges, through pixel centres (an edge of the bar then runs
+    # between two rows of centres, not through one), at the first camera's place on the depth axis
+    px0, py = np.floor(0.04 * size) + 0.5, np.floor(0.96 * size) + 0.5
+    a, b, c = (0, 2, 1) if p["view"] == "top" else (2, 1, 0)
+    ends = np.zeros((2, 3), np.float64)
+    for k, px in enumerate((px0, px0 + bar / mpp)):
+        ends[k, a] = (px - view[0, 3]) / view[0, a]
+        ends[k, b] = (py - view[1, 3]) / view[1, b]
+        ends[k, c] = pos[0, c]
+    return view, mpp, bar, ends
+
+
+def _trajectory_plot(tr, both, scene, m, p, path, device, backend=None):
+    """The picture of `--save_plot`.  The view comes from the host copy of the trajectories that the
+    evaluation's read-back delivered; everything drawn is still on the device: the map's voxels underneath
+    (`SceneMap.render`), then, each above the one before, the ground truth (layer 1), the aligned prediction (layer 2),
+    the start disc and the scale bar (layer 3).  One read-back: the finished picture with the counters."""
+    from . import pointcloud
+    view, mpp, bar, ends = plot_layout(both, p)
+    canvas = pointcloud.Canvas(p["size"], p["size"], device, backend)
+    view_dev = upload(view, device)
+    F = tr.aligned.numel() // 16
+    with torch.no_grad():
+        if scene is not None:
+            scene.render(canvas, view_dev, min_points=m["min_points"], size=p["point_size"])
+        gt_xyz = tr.gt_traj.reshape(F, 16)[:, 3::4][:, :3].contiguous()
+        pred_xyz = tr.aligned.reshape(F, 16)[:, 3::4][:, :3].contiguous()
+        canvas.lines(gt_xyz, view=view_dev, colour=PLOT_GT, width=3.0, layer=1)
+        canvas.lines(pred_xyz, view=view_dev, colour=PLOT_PRED, width=2.0, layer=2)
+        canvas.lines(gt_xyz[:1], view=view_dev, colour=PLOT_START, width=9.0, layer=3)
+        canvas.lines(ends, view=view_dev, colour=PLOT_BAR, width=3.0, layer=3)
+        stats = canvas.save(path)
+    stats.update(view=p["view"], m_per_px=mpp, scale_bar=bar)
     return stats

@@ -148,7 +148,8 @@ class DepthPredictor:
             off += ops.viz_granule(npx)
         return results
 
-    def predict_cloud(self, images, inv_K=None, scale=1.0, max_depth=None, stride=1, post_process=False):
+    def predict_cloud(self, images, inv_K=None, scale=1.0, max_depth=None, stride=1, post_process=False, view=None,
+                      view_size=3):
         """The coloured point cloud of every image: one structured array (`pointcloud.VERTEX_DTYPE`: x, y, z, red,
         green, blue, alpha) per image, ready for `pointcloud.write_ply`.  The same network pass as `predict`; the
         scaled disparity min_disp + (max_disp - min_disp) * disp at network size goes through ONE `ops.point_cloud`
@@ -157,9 +158,13 @@ class DepthPredictor:
         ([3,3] for all images or one per image; default: the KITTI intrinsics scaled to each image,
         `pointcloud.intrinsics`) and colours every point with its pixel of the uploaded image.  Points beyond
         `max_depth` (default: the predictor's `max_depth * scale`) are dropped, as is anything that is not a depth (a
-        negative or non-finite value).  There is no near limit: the sigmoid bounds the disparity."""
+        negative or non-finite value).  There is no near limit: the sigmoid bounds the disparity.
+
+        `view=(yaw, pitch)` in degrees also draws every cloud as its camera sees it after a turn about the point on
+        the optical axis at the cloud's median depth (`cloud_views`), every point a square of `view_size` pixels, and
+        returns (clouds, pictures): one uint8 [H,W,3] array per image, at the image's size."""
         if not len(images):
-            return []
+            return [] if view is None else ([], [])
         sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
         if inv_K is None:
             inv_K = np.stack([pointcloud.intrinsics(H0, W0) for H0, W0 in sizes])
@@ -180,7 +185,31 @@ class DepthPredictor:
             cloud = ops.point_cloud(scaled, ops.cloud_rows(sizes), inv_K, rgb=src, stride=stride,
                                     min_depth=0.0, max_depth=far, pred_is_disp=True,
                                     scale_factor=scale, backend=self.backend)
-            return pointcloud.cloud_arrays(*cloud)
+            clouds = pointcloud.cloud_arrays(*cloud)
+            if view is None:
+                return clouds
+            return clouds, cloud_views(cloud, clouds, sizes, inv_K, view, view_size, self.backend)
+
+
+def cloud_views(cloud, clouds, sizes, inv_K, view, size=3, backend=None):
+    """Every cloud of an `ops.point_cloud` batch (`cloud` = its vertices, counts, offsets, still on the device) drawn at
+    its image's size from the camera turned by `view` = (yaw, pitch) degrees: uint8 [H,W,3] arrays.  The pivot of the
+    turn lies on the optical axis at the median depth of the kept points, taken on the host from `clouds`, the copy
+    `pointcloud.cloud_arrays` has already read back (the export keeps no median on the device without a metrics row);
+    the points themselves are drawn from the device buffer.  One read-back per picture."""
+    vertices, counts, offsets = cloud
+    inv_K = np.asarray(inv_K, np.float64)
+    inv_K = inv_K[None].repeat(len(sizes), 0) if inv_K.ndim == 2 else inv_K
+    pictures = []
+    for i, (H, W) in enumerate(sizes):
+        canvas = pointcloud.Canvas(W, H, vertices.device, backend)
+        if len(clouds[i]):
+            pivot = float(np.median(clouds[i]["z"].astype(np.float64)))
+            V = pointcloud.orbit_view(np.linalg.inv(inv_K[i][:3, :3]), view[0], view[1], pivot)
+            end = vertices.numel() if i + 1 == len(sizes) else int(offsets[i + 1]) * pointcloud.CLOUD_VERTEX
+            canvas.points(vertices[int(offsets[i]) * pointcloud.CLOUD_VERTEX:end], count=counts[i:i + 1], view=V, size=size)
+        pictures.append(canvas.read()[0])
+    return pictures
 
 
 def _to_host(t):
@@ -213,6 +242,11 @@ def parse_args(argv=None):
     parser.add_argument("--cloud_max_depth", type=float, default=None,
                         help="points beyond this depth are dropped (default: the model's max depth times cloud_scale)")
     parser.add_argument("--cloud_stride", type=int, default=1, help="export every N-th pixel in both directions")
+    parser.add_argument("--cloud_view", type=float, nargs=2, default=None, metavar=("YAW", "PITCH"),
+                        help="with --point_cloud: also write <name>_Base_view.png, the cloud seen by the camera turned "
+                             "by these degrees about the point at the median depth on its optical axis")
+    parser.add_argument("--cloud_view_size", type=int, default=3, choices=[1, 3, 5, 7],
+                        help="side of a point's square in the view, in pixels")
     camera = parser.add_mutually_exclusive_group()
     camera.add_argument("--fov", type=float, default=None, metavar="DEG",
                         help="horizontal field of view of the camera in degrees (default: the KITTI intrinsics)")
@@ -225,6 +259,8 @@ def parse_args(argv=None):
         parser.error("--cloud_stride must be at least 1")
     if args.cloud_scale <= 0:
         parser.error("--cloud_scale must be positive")
+    if args.cloud_view is not None and not args.point_cloud:
+        parser.error("--cloud_view needs --point_cloud")
     return args
 
 
@@ -261,6 +297,14 @@ def _save_cloud(out_dir, path, cloud):
     return pointcloud.write_ply(os.path.join(out_dir, "{}_Base.ply".format(stem)), cloud)
 
 
+def _save_view(out_dir, path, picture):
+    import PIL.Image as pil
+    stem = os.path.splitext(os.path.basename(path))[0]
+    dest = os.path.join(out_dir, "{}_Base_view.png".format(stem))
+    pil.fromarray(picture).save(dest)
+    return dest
+
+
 def _cloud_inv_K(args, images):
     return np.stack([pointcloud.intrinsics(im.shape[0], im.shape[1], fov=getattr(args, "fov", None),
                                            fxfycxcy=getattr(args, "intrinsics", None)) for im in images])
@@ -269,7 +313,7 @@ def _cloud_inv_K(args, images):
 def run_cli(args, predictor=None):
     """Body of test_simple.py.  `predictor` may be injected (tests); by default it is loaded from `args.weights`.
     With `--point_cloud` every batch also goes through `predict_cloud` (a second network pass: `predict` is left as it
-    is) and `<name>_Base.ply` is written next to the JPEG.
+    is) and `<name>_Base.ply` is written next to the JPEG; `--cloud_view YAW PITCH` adds `<name>_Base_view.png`.
     Returns the list of written JPEG paths."""
     paths, out_dir = find_inputs(args.image_path, args.save_path, args.ext)
     if predictor is None:
@@ -294,9 +338,14 @@ def run_cli(args, predictor=None):
                 results = predictor.predict(images, want_float=args.save_npy)
             pending += [pool.submit(_save, out_dir, p, r, args.save_npy) for p, r in zip(chunk, results)]
             if getattr(args, "point_cloud", False):
-                clouds = predictor.predict_cloud(images, inv_K=_cloud_inv_K(args, images), scale=args.cloud_scale,
-                                                 max_depth=args.cloud_max_depth, stride=args.cloud_stride,
-                                                 post_process=bool(getattr(args, "post_process", False)))
+                kw = dict(inv_K=_cloud_inv_K(args, images), scale=args.cloud_scale, max_depth=args.cloud_max_depth,
+                          stride=args.cloud_stride, post_process=bool(getattr(args, "post_process", False)))
+                if getattr(args, "cloud_view", None) is not None:        # as above: the keyword only when it is set
+                    clouds, pictures = predictor.predict_cloud(images, view=tuple(args.cloud_view),
+                                                               view_size=getattr(args, "cloud_view_size", 3), **kw)
+                    cloud_saves += [pool.submit(_save_view, out_dir, p, v) for p, v in zip(chunk, pictures)]
+                else:
+                    clouds = predictor.predict_cloud(images, **kw)
                 cloud_saves += [pool.submit(_save_cloud, out_dir, p, c) for p, c in zip(chunk, clouds)]
         written = [f.result() for f in pending]
         for f in cloud_saves:

@@ -1922,6 +1922,112 @@ def map_finish(state, voxel, min_points=1, backend=None):
     return out_keys, vertices, out_counts, m
 
 
+# ---------------------------------------------------------------------------- views (rasterised points and polylines)
+ViewState = collections.namedtuple("ViewState", "cells counters H W")
+ViewState.__doc__ = """The caller-owned canvas of the `bbd_view_*` entries: `cells` int64 [H,W] (the uint64 keys, empty =
+-1), `counters` int64 [4] (offered, drawn, clipped, rejected points)."""
+
+
+def pack_rgb(colour, what):
+    """(r, g, b) bytes -> r | g << 8 | b << 16."""
+    c = [int(v) for v in colour]
+    if len(c) != 3 or min(c) < 0 or max(c) > 255:
+        raise ValueError("%s: a colour is three bytes, got %r" % (what, colour))
+    return c[0] | (c[1] << 8) | (c[2] << 16)
+
+
+def view_state(height, width, device, backend=None):
+    """A cleared `ViewState` of height x width cells."""
+    H, W = int(height), int(width)
+    if H < 1 or W < 1 or H * W > _lib.VIEW_MAX_CELLS:
+        raise ValueError("view_state: a canvas has at least 1 x 1 and at most 2^28 cells, got %d x %d" % (H, W))
+    state = ViewState(torch.empty(H, W, dtype=torch.int64, device=device),
+                      torch.empty(_lib.VIEW_COUNTERS, dtype=torch.int64, device=device), H, W)
+    view_clear(state, backend)
+    return state
+
+
+def _view_state_args(state, backend):
+    cells, counters, H, W = state
+    assert cells.dtype == torch.int64 and tuple(cells.shape) == (H, W) and cells.is_contiguous()
+    assert counters.dtype == torch.int64 and counters.numel() == _lib.VIEW_COUNTERS
+    backend._check(cells, counters)
+    return ptr(cells), ptr(counters), int(H), int(W)
+
+
+def _view_matrix(view, device, what):
+    """The float64 [4,4] view on `device`: a device tensor is taken as it is, a host array is uploaded."""
+    if not torch.is_tensor(view):
+        view = torch.as_tensor(np.ascontiguousarray(view, dtype=np.float64))
+    if view.dtype != torch.float64 or view.numel() != 16 or tuple(view.shape) not in ((4, 4), (16,)):
+        raise ValueError("%s: view must be float64 [4,4], got %s %s" % (what, view.dtype, tuple(view.shape)))
+    return view.contiguous() if view.device == device else upload(view.contiguous(), device)
+
+
+def view_clear(state, backend=None):
+    """`bbd_view_clear`: every cell empty, the counters zero (one launch)."""
+    backend = backend or default_backend()
+    backend.run("bbd_view_clear", state.cells, *_view_state_args(state, backend))
+
+
+def view_points(state, vertices, view, count=None, size=1, backend=None):
+    """`bbd_view_points` (one launch, nothing read back): the 16-byte vertex records of `vertices` (uint8 [16 n], as
+    `point_cloud` and `map_finish` leave them) go into the canvas through `view` (float64 [4,4], host or device).
+    `count`: None, or an int32 DEVICE tensor of one element - only the first min(count, n) records are read."""
+    backend = backend or default_backend()
+    if vertices.dtype != torch.uint8 or vertices.dim() != 1 or vertices.numel() % _lib.CLOUD_VERTEX:
+        raise ValueError("view_points: vertices must be uint8 [16 n], got %s %s" % (vertices.dtype, tuple(vertices.shape)))
+    if int(size) not in (1, 3, 5, 7):
+        raise ValueError("view_points: size must be 1, 3, 5 or 7, got %r" % (size,))
+    dev = state.cells.device
+    if vertices.device != dev or (count is not None and count.device != dev):
+        raise ValueError("view_points: vertices and count must be on the canvas's device %s" % dev)
+    if count is not None and (count.dtype != torch.int32 or count.numel() != 1):
+        raise ValueError("view_points: count must be one int32, got %s %s" % (count.dtype, tuple(count.shape)))
+    vertices = vertices.contiguous()
+    if vertices.data_ptr() % _lib.CLOUD_VERTEX:
+        raise ValueError("view_points: vertices must be 16-byte aligned")
+    V = _view_matrix(view, dev, "view_points")
+    backend._check(vertices, count, V)
+    n = vertices.numel() // _lib.CLOUD_VERTEX
+    # `count` may be a view into a larger tensor: its address is taken as it is
+    backend.run("bbd_view_points", vertices, *_view_state_args(state, backend), ptr(vertices),
+                ctypes.c_void_p(0 if count is None else count.data_ptr()), n, ptr(V), int(size))
+
+
+def view_lines(state, xyz, view, colour=(0, 0, 0), width=2.0, layer=0, closed=False, backend=None):
+    """`bbd_view_lines` (one launch, nothing read back): the polyline through `xyz` (float64 [P,3] world positions, host
+    or device) as an overlay of `colour` on `layer` (0 .. 65535; a higher layer covers a lower one, every layer covers
+    the points).  One position, or a segment without length, draws a disc of diameter `width` pixels."""
+    backend = backend or default_backend()
+    dev = state.cells.device
+    if not torch.is_tensor(xyz):
+        xyz = torch.as_tensor(np.ascontiguousarray(xyz, dtype=np.float64))
+    if xyz.dtype != torch.float64 or xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1:
+        raise ValueError("view_lines: xyz must be float64 [P,3] with P >= 1, got %s %s" % (xyz.dtype, tuple(xyz.shape)))
+    width, layer = float(width), int(layer)
+    if not (width > 0.0 and np.isfinite(width)):
+        raise ValueError("view_lines: the width must be positive and finite, got %r" % (width,))
+    if not 0 <= layer <= _lib.VIEW_MAX_LAYER:
+        raise ValueError("view_lines: the layer must lie in [0, %d], got %d" % (_lib.VIEW_MAX_LAYER, layer))
+    rgb = pack_rgb(colour, "view_lines")
+    xyz = xyz.contiguous() if xyz.device == dev else upload(xyz.contiguous(), dev)
+    V = _view_matrix(view, dev, "view_lines")
+    backend._check(xyz, V)
+    backend.run("bbd_view_lines", xyz, *_view_state_args(state, backend), ptr(xyz), int(xyz.shape[0]), ptr(V), rgb,
+                width, layer, 1 if closed else 0)
+
+
+def view_resolve(state, background=(255, 255, 255), backend=None):
+    """`bbd_view_resolve` (one launch): the canvas as uint8 [H,W,3] on the device, `background` where nothing was
+    drawn.  The cells are only read."""
+    backend = backend or default_backend()
+    cells_p, _, H, W = _view_state_args(state, backend)
+    out = torch.empty(H, W, 3, dtype=torch.uint8, device=state.cells.device)
+    backend.run("bbd_view_resolve", state.cells, cells_p, H, W, pack_rgb(background, "view_resolve"), ptr(out))
+    return out
+
+
 # ---------------------------------------------------------------------------- flip post-processing
 def post_process_disp(disp, backend=None):
     """Monodepth2's `batch_post_process_disparity(l, r[:, :, ::-1])` in ONE `bbd_post_process_disp` launch: `disp`

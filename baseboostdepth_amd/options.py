@@ -110,6 +110,16 @@ class MonodepthOptions:
         self.parser.add_argument("--map_min_points", type=int, default=1, help="drop voxels with fewer points")
         self.parser.add_argument("--map_capacity", type=int, default=1 << 24,
                                  help="slots of the voxel table (rounded up to a power of two, 48 bytes each)")
+        # the bird's-eye plot of the run: both trajectories over the scene map, drawn on the device
+        self.parser.add_argument("--save_plot", type=str, default=None, metavar="FILE.png",
+                                 help="with --trajectory: write a picture of the ground-truth and the aligned predicted "
+                                      "trajectory seen from above, over the scene map where --save_map is given")
+        self.parser.add_argument("--plot_view", type=str, default="top", choices=["top", "side"])
+        self.parser.add_argument("--plot_size", type=int, default=1024, help="the picture is this many pixels square")
+        self.parser.add_argument("--plot_ceiling", type=float, default=3.0,
+                                 help="top view: voxels more than this far above the highest camera are left out")
+        self.parser.add_argument("--plot_point_size", type=int, default=1, choices=[1, 3, 5, 7],
+                                 help="side of a voxel's square in pixels")
 
     def parse(self, argv=None):
         self.options = self.parser.parse_args(argv)

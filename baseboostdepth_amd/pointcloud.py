@@ -7,6 +7,9 @@ bytes as they came from the device.  Nothing here touches a point.
 
 `SceneMap` fuses the clouds of many posed frames on a voxel grid (`ops.map_*`) and reads the finished
 voxels back once, as one array of the same vertex record.
+
+`Canvas` draws such vertices, and polylines such as trajectories, into a picture on the device (`ops.view_*`, DESIGN.md
+6k); `ortho_view` and `orbit_view` make the view matrices it takes.
 """
 import numpy as np
 import torch
@@ -122,6 +125,120 @@ def read_ply(path):
     return np.frombuffer(body, dtype=VERTEX_DTYPE).copy()
 
 
+def ortho_view(lo, hi, width, height, plane="top", margin=0.05, near=None):
+    """An orthographic view of the world box [lo, hi] (three coordinates each) for a `width` x `height` canvas:
+    (float64 [4,4], metres per pixel).  The box's two plotted axes are fitted into the canvas less `margin` of it on
+    every side, with one scale for both, and centred.  `plane="top"`: u along +x, v along -z (forward is up), depth =
+    y - near - KITTI's y points down, so the viewer is above; `plane="side"`: u along +z, v along +y, depth = x - near.
+    Whatever lies before `near` on the depth axis is clipped; None puts it a kilometre before the box."""
+    lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+    if plane not in ("top", "side"):
+        raise ValueError("ortho_view: the plane is 'top' or 'side', got %r" % (plane,))
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (lo <= hi).all()):
+        raise ValueError("ortho_view: the box must be finite with lo <= hi, got %s, %s" % (lo, hi))
+    if not 0.0 <= float(margin) < 0.5:
+        raise ValueError("ortho_view: the margin must lie in [0, 0.5), got %r" % (margin,))
+    a, b, c = (0, 2, 1) if plane == "top" else (2, 1, 0)             # the axes along u, along v, and of the depth
+    inner = 1.0 - 2.0 * float(margin)
+    extent = max((hi[a] - lo[a]) / (inner * width), (hi[b] - lo[b]) / (inner * height))
+    mpp = float(extent) if extent > 0.0 else 1.0                     # a box without extent: a metre per pixel
+    s = 1.0 / mpp
+    ca, cb = 0.5 * (lo[a] + hi[a]), 0.5 * (lo[b] + hi[b])
+    near = float(lo[c] - 1000.0 if near is None else near)
+    flip = -1.0 if plane == "top" else 1.0
+    V = np.zeros((4, 4), np.float64)
+    V[0, a], V[0, 3] = s, 0.5 * width - s * ca
+    V[1, b], V[1, 3] = flip * s, 0.5 * height - flip * s * cb
+    V[2, c], V[2, 3] = 1.0, -near
+    V[3, 3] = 1.0
+    return V, mpp
+
+
+def orbit_view(K, yaw_deg, pitch_deg, pivot):
+    """The perspective view (float64 [4,4]) of the camera `K` (3x3 or 4x4, in pixels) after it has been turned about
+    the point at depth `pivot` on its optical axis - `yaw_deg` about the y axis, then `pitch_deg` about the x axis -
+    keeping its distance from that point.  Positions are in the frame of the camera before the turn, as the vertices
+    of `ops.point_cloud` are.  Rows 2 and 3 are both the depth in the turned camera."""
+    K = np.asarray(K, np.float64)
+    if K.shape not in ((3, 3), (4, 4)):
+        raise ValueError("orbit_view: K must be 3x3 or 4x4, got %s" % (K.shape,))
+    pivot = float(pivot)
+    if not (pivot > 0.0 and np.isfinite(pivot)):
+        raise ValueError("orbit_view: the pivot's depth must be positive and finite, got %r" % (pivot,))
+    y, p = np.deg2rad(float(yaw_deg)), np.deg2rad(float(pitch_deg))
+    Ry = np.array([[np.cos(y), 0, np.sin(y)], [0, 1, 0], [-np.sin(y), 0, np.cos(y)]])
+    Rx = np.array([[1, 0, 0], [0, np.cos(p), -np.sin(p)], [0, np.sin(p), np.cos(p)]])
+    R = Ry @ Rx                                                      # the turned camera's axes in the old frame
+    centre = np.array([0.0, 0.0, pivot])
+    E = np.eye(4)
+    E[:3, :3] = R.T
+    E[:3, 3] = centre - R.T @ centre                                 # X' = R^T (X - pivot) + pivot along the axis
+    P = np.zeros((4, 4))
+    P[0, :3], P[1, :3] = K[0, :3], K[1, :3]
+    P[2, 2] = P[3, 2] = 1.0
+    return np.ascontiguousarray(P @ E)
+
+
+class Canvas:
+    """A picture drawn on the device (`bbd_view_*`): `width` x `height` cells of one 64-bit key each.
+    `points` and `lines` launch one kernel per call and read nothing back; what the canvas shows does not depend on
+    the order of the calls."""
+
+    STATS = ("offered", "drawn", "clipped", "rejected")
+
+    def __init__(self, width, height, device="cuda:0", backend=None):
+        from . import ops
+        self.backend = backend or ops.default_backend()
+        self.device = torch.device(device)
+        self.width, self.height = int(width), int(height)
+        self.state = ops.view_state(self.height, self.width, self.device, self.backend)
+
+    def clear(self):
+        from . import ops
+        ops.view_clear(self.state, self.backend)
+
+    def points(self, vertices, count=None, view=None, size=1):
+        """16-byte vertex records (uint8 [16 n] on the device); `count`: a device int32 that limits them, or None."""
+        from . import ops
+        ops.view_points(self.state, vertices, view, count=count, size=size, backend=self.backend)
+
+    def lines(self, xyz, view=None, colour=(0, 0, 0), width=2.0, layer=0, closed=False):
+        """A polyline through float64 [P,3] world positions, above every point; a higher layer covers a lower one."""
+        from . import ops
+        ops.view_lines(self.state, xyz, view, colour=colour, width=width, layer=layer, closed=closed,
+                       backend=self.backend)
+
+    def image(self, background=(255, 255, 255)):
+        """uint8 [H,W,3] on the device."""
+        from . import ops
+        return ops.view_resolve(self.state, background, self.backend)
+
+    def read(self, background=(255, 255, 255)):
+        """(image as numpy uint8 [H,W,3], stats) in ONE pinned read-back of the picture and the counters."""
+        packed = torch.cat([self.image(background).reshape(-1), self.state.counters.view(torch.uint8)])
+        if packed.is_cuda:
+            host = torch.empty(packed.shape, dtype=torch.uint8, pin_memory=True)
+            host.copy_(packed, non_blocking=True)
+            torch.cuda.current_stream(packed.device).synchronize()
+        else:
+            host = packed
+        flat = host.numpy()
+        n = 3 * self.height * self.width
+        counters = flat[n:].copy().view(np.int64)
+        return flat[:n].reshape(self.height, self.width, 3).copy(), dict(zip(self.STATS, (int(c) for c in counters)))
+
+    def save(self, path, background=(255, 255, 255)):
+        """Writes the picture (PNG by the name's ending, through Pillow); returns the stats of `read`."""
+        import PIL.Image as pil
+        image, stats = self.read(background)
+        pil.fromarray(image).save(path)
+        return stats
+
+    def stats(self):
+        """The counters of `points` - offered, drawn, clipped, rejected - as a dict (a read-back of 32 bytes)."""
+        return dict(zip(self.STATS, (int(c) for c in self.state.counters.cpu().tolist())))
+
+
 class SceneMap:
     """A scene map: the points of posed frames fused on a grid of `voxel`-sized cells, one coloured vertex per occupied
     cell (`bbd_map_*`).  The state - an open-addressing hash table of `capacity` slots, rounded up to a
@@ -193,3 +310,11 @@ class SceneMap:
         assert M <= R
         verts = flat[:4 * M].copy().view(np.uint8).view(VERTEX_DTYPE)
         return verts, flat[4 * R:4 * R + M].copy(), stats
+
+    def render(self, canvas, view, min_points=1, size=1):
+        """The voxels with at least `min_points` points into `canvas`: `ops.map_finish`, then `canvas.points` on its
+        vertices and their device-side count, in slot order - a canvas does not care.  Nothing is read back; the state
+        is left as `finish` leaves it."""
+        from . import ops
+        _, vertices, _, m = ops.map_finish(self.state, self.voxel, min_points, self.backend)
+        canvas.points(vertices, count=m, view=view, size=size)

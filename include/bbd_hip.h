@@ -40,8 +40,9 @@ extern "C" {
  * 11 = bbd_pose_ate (KITTI odometry evaluation: chained poses, local ground truth, trajectory error);
  * 12 = bbd_post_process_disp (depth evaluation: flip post-processing of the predicted disparities);
  * 14 = bbd_pose_trajectory (KITTI odometry: full-trajectory t_rel, r_rel and aligned ATE);
- * 15 = bbd_point_cloud (coloured point clouds); 16 = bbd_map_* (voxel-fused scene map). */
-#define BBD_ABI_VERSION 16
+ * 15 = bbd_point_cloud (coloured point clouds); 16 = bbd_map_* (voxel-fused scene map);
+ * 17 = bbd_view_* (points and polylines rasterised into a z-buffered canvas). */
+#define BBD_ABI_VERSION 17
 
 /* Source frames live in separate tensors, one per frame id (inputs[("color", f, 0)],
  * trainer.py:428).  A "slot" indexes a host array of their base pointers. */
@@ -594,6 +595,53 @@ int bbd_map_accumulate(uint64_t* keys, uint64_t* pos, uint32_t* col, int64_t* co
 int bbd_map_finish(const uint64_t* keys, const uint64_t* pos, const uint32_t* col, int T, int min_points, double voxel,
                    int64_t* out_keys, void* vertices, int32_t* out_counts, int32_t* m, int32_t* scratch,
                    int scratch_ints, void* stream);
+
+/* ---- Views (csrc/bbd_view.hip, pointcloud.Canvas): points and polylines rasterised into a z-buffered
+ * canvas, resolved to RGB bytes.  The canvas is the caller's:
+ *   cells     uint64 [H,W]   one key per pixel, empty = all ones
+ *   counters  int64 [BBD_VIEW_COUNTERS] = {offered, drawn, clipped, rejected} points, running totals
+ * A key is rank << 32 | colour, colour = r << 24 | g << 16 | b << 8 | 0xff.  The rank of a point at view depth d > 0 is
+ * 0x80000000 | (bits((float)d) >> 1); the rank of an overlay primitive is 0x7fffffff - layer, 0 <= layer < 2^16.  Every
+ * write is an unsigned 64-bit atomic minimum, so the finished canvas does not depend on the order of lanes, launches or
+ * calls: the nearer point wins, every overlay beats every point, a higher layer beats a lower one, an exact tie goes to
+ * the smaller colour word.
+ *
+ * A world position (x, y, z) is projected by `view`, a DEVICE float64 row-major 4x4, in float64:
+ *   p_r = ((V[4r] x + V[4r+1] y) + V[4r+2] z) + V[4r+3];  u = p_0 / p_3, v = p_1 / p_3, d = p_2
+ * (an orthographic view has the last row 0 0 0 1; a perspective view repeats row 3 in row 2).  It is REJECTED when any
+ * of u, v, d, p_3 is not finite (p_3 = 0 is: the quotients are not finite), else BEHIND when p_3 <= 0 or d <= 0.
+ * Operation by operation: csrc/bbd_view_math.h, -ffp-contract=off.
+ *
+ * bbd_view_clear: every cell empty, the counters zero.  One launch.
+ *
+ * bbd_view_points draws the first min(*count, n_max) records of `vertices` (BBD_CLOUD_VERTEX bytes each: x y z float32,
+ *   then r g b a; 16-byte aligned), all n_max with count = NULL.  `count` is a DEVICE int32 read by the kernel; records
+ *   past it are never read.  A point that is not rejected or behind covers the size x size pixels centred on pixel
+ *   (floor(u), floor(v)), size in {1, 3, 5, 7}, cut to the canvas; it is CLIPPED when it is behind or the square misses
+ *   the canvas, else DRAWN.  counters: offered += records visited, and one of drawn, clipped, rejected per record.
+ *   One launch, a lane per record; nothing is launched for n_max = 0.
+ *
+ * bbd_view_lines draws the polyline through the P world positions xyz (float64 [P,3]) as an overlay of one colour
+ *   (rgb = r | g << 8 | b << 16) and layer: P - 1 segments, one more back to the first vertex with closed = 1 and P > 2.
+ *   P = 1 and a segment of no length draw a disc.  A segment with an end that is rejected or behind is skipped.  Pixel
+ *   (i, j) is painted when the squared distance of (i + 0.5, j + 0.5) from the projected segment is <= (width / 2)^2.
+ *   One launch, a wave per segment; a segment costs its bounding box cut to the canvas.  The counters are the points':
+ *   they are left as they are.
+ *
+ * bbd_view_resolve writes out uint8 [H,W,3]: the colour of every cell, background_rgb (r | g << 8 | b << 16) where it
+ *   is empty.  One launch; the cells are only read.
+ *
+ * No allocation, no host synchronisation.  A NULL pointer (other than count), H or W below 1, n_max below 0, P below 1,
+ * vertices not 16-byte aligned, a size other than 1, 3, 5, 7, a width that is not positive and finite, a layer outside
+ * [0, 65535], a colour outside [0, 0xffffff] or closed other than 0 or 1 return BBD_E_BADARG; H * W > 2^28 returns
+ * BBD_E_TOOMANY.  Nothing is launched then. */
+#define BBD_VIEW_COUNTERS 4
+int bbd_view_clear(uint64_t* cells, int64_t* counters, int H, int W, void* stream);
+int bbd_view_points(uint64_t* cells, int64_t* counters, int H, int W, const void* vertices, const int32_t* count,
+                    int n_max, const double* view, int size, void* stream);
+int bbd_view_lines(uint64_t* cells, int64_t* counters, int H, int W, const double* xyz, int P, const double* view,
+                   int rgb, double width, int layer, int closed, void* stream);
+int bbd_view_resolve(const uint64_t* cells, int H, int W, int background_rgb, uint8_t* out, void* stream);
 
 /* Flip post-processing of predicted disparities (Monodepth2's batch_post_process_disparity; evaluate_depth.py
  * --post_process), n images per call.
