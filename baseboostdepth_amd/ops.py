@@ -4,7 +4,8 @@ PyTorch is plumbing here (device memory, streams, autograd tape); all arithmetic
 path runs in baseboostdepth_amd/csrc/bbd_kernels.hip.  `HipBackend` is the only backend the
 product has: it refuses non-GPU tensors and raises if the extension is missing.  (The CPU test
 tier injects a host build of the same arithmetic through the `backend=` seam - see
-tests/host_port.py - but nothing in this package can fall back to it.)
+tests/ports.py - but nothing in this package can fall back to it.  A backend provides `name`, `lib`, `_check`, `run`,
+`num_tiles*`, `smooth_chunks` and `fused_work_items`.)
 """
 import collections
 import ctypes

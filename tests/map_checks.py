@@ -2,7 +2,7 @@
 tier (tests/test_gpu_map.py: the device).  Test infrastructure only.
 
 Three checks:
-  1 fusion     from the per-point (key, q, rgb) the host port produced (`MapPortBackend.points`), the numpy fusion
+  1 fusion     from the per-point (key, q, rgb) the host port produced (`port_points`), the numpy fusion
                (`map_ref.fuse`) must give the vertices, counts and order of the implementation under test, byte for byte.
                The device is held to the port's per-point values: it must equal the port's result byte for byte.
   2 per point  the port's world positions (v + q / 65536) voxel lie within tau + voxel / 65536 of the float64 reference's:
@@ -14,6 +14,7 @@ Three checks:
 
 Shapes are the smallest at which the kernel can go wrong: 3 frames of 12 x 20, strides 1 and 2, a window that cuts two
 rows and three columns."""
+import ctypes
 import functools
 
 import numpy as np
@@ -150,10 +151,31 @@ def same_bytes(a, b):
     return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
+def port_points(port, disp, rgb, poses, inv_K, scale, window, stride, min_depth, max_depth, voxel, is_depth):
+    """What `bbd_map_point` makes of every candidate of a call (numpy inputs): verdict int32 [G], key int64 [G],
+    q uint32 [G,3], rgb uint32 [G,3]; key, q and rgb are meaningful where verdict == 1 (kept)."""
+    disp, rgb = np.ascontiguousarray(disp, np.float32), np.ascontiguousarray(rgb, np.float32)
+    poses, inv_K = np.ascontiguousarray(poses, np.float64).reshape(-1, 16), np.ascontiguousarray(inv_K, np.float32)
+    n, h, w = disp.shape
+    G = n * h * w
+    verdict, key = np.zeros(G, np.int32), np.zeros(G, np.int64)
+    q, col = np.zeros((G, 3), np.uint32), np.zeros((G, 3), np.uint32)
+    sc = None if scale is None else np.array([scale], np.float64)
+    p = lambda a: ctypes.c_void_p(0 if a is None else a.ctypes.data)   # noqa: E731
+    r0, r1, c0, c1 = window or (0, h, 0, w)
+    fn = port.dll.hp_map_points
+    fn.restype = ctypes.c_int
+    got = fn(p(disp), p(rgb), p(poses), p(inv_K), p(sc), *[ctypes.c_int(v) for v in (n, h, w, r0, r1, c0, c1, stride)],
+             ctypes.c_double(min_depth), ctypes.c_double(max_depth), ctypes.c_double(voxel),
+             ctypes.c_int(1 if is_depth else 0), p(verdict), p(key), p(q), p(col))
+    assert 0 <= got <= G, got
+    return verdict[:got], key[:got], q[:got], col[:got]
+
+
 def check(name, out, counts4, port):
     """Checks 1 to 3 of a finished case against the port's per-point values and the float64 reference."""
     case = make(name)
-    verdict, key, q, col = port.points(case["disp"], case["rgb"], case["poses"], INV_K, **call_kw(case))
+    verdict, key, q, col = port_points(port, case["disp"], case["rgb"], case["poses"], INV_K, **call_kw(case))
     want = reference(name)
     kept = verdict == ref.KEPT
     t = tau(case)

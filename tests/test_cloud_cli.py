@@ -1,6 +1,6 @@
 """CPU tier of the point-cloud command lines: PLY files, intrinsics, `test_simple.py --point_cloud` with a stub predictor
 and `evaluate_depth.py --save_clouds` on synthetic KITTI and SYNS splits, the kernels replaced by their host ports
-(tests/cloud_port.py)."""
+(tests/ports.py)."""
 import os
 import sys
 
@@ -33,8 +33,8 @@ end_header
 
 @pytest.fixture(scope="module")
 def port():
-    from cloud_port import CloudPortBackend
-    return CloudPortBackend()
+    from ports import PortBackend
+    return PortBackend()
 
 
 # ---------------------------------------------------------------------------------------------- files and intrinsics

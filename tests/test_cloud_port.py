@@ -13,13 +13,13 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import cloud_checks as C  # noqa: E402
 import cloud_ref  # noqa: E402
-from cloud_port import CloudPortBackend  # noqa: E402
+from ports import PortBackend  # noqa: E402
 from baseboostdepth_amd import _lib, ops, pointcloud  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def port():
-    return CloudPortBackend()
+    return PortBackend()
 
 
 @pytest.mark.parametrize("check", C.ALL_CHECKS, ids=lambda f: f.__name__)

@@ -97,8 +97,8 @@ def test_csv_format(tmp_path):
 
 @pytest.fixture(scope="module")
 def port():
-    from compare_port import ComparePortBackend
-    return ComparePortBackend()
+    from ports import PortBackend
+    return PortBackend()
 
 
 def _predictors(port):

@@ -13,13 +13,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import compare_checks as C  # noqa: E402
-from compare_port import ComparePortBackend  # noqa: E402
+from ports import PortBackend  # noqa: E402
 from baseboostdepth_amd import _lib, evaluation, inference, ops  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def port():
-    return ComparePortBackend()
+    return PortBackend()
 
 
 @pytest.fixture(scope="module")

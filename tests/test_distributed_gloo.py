@@ -164,7 +164,7 @@ def _worker_shard(rank, world, port, q):
     _setup(rank, world, port)
     from golden_io import Case
     from fused_runner import run_direct_case
-    from host_port import HostPortBackend
+    from ports import PortBackend
     case = Case("md2_b2_32x64")
     b = rank                                   # one sample per rank
     for k in list(case.inputs):
@@ -177,7 +177,7 @@ def _worker_shard(rank, world, port, q):
     case.disp = {s: d.detach()[b:b + 1].clone().requires_grad_(True) for s, d in case.disp.items()}
     case.poses = {f: T.detach()[b:b + 1].clone().requires_grad_(True) for f, T in case.poses.items()}
     case.noise = case.noise[b:b + 1].contiguous()
-    tr, inputs, outputs, losses = run_direct_case(case, HostPortBackend(), materialize=False)
+    tr, inputs, outputs, losses = run_direct_case(case, PortBackend(), materialize=False)
     losses["loss"].backward()
     loss = losses["loss"].detach().clone()
     dist.all_reduce(loss, op=dist.ReduceOp.SUM)

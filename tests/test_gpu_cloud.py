@@ -32,7 +32,7 @@ def test_kernels(hip, check):
 def workload():
     """4 images of 375 x 1242 from a 192 x 640 disparity, ground truth with holes, colours: inputs, and the port's
     answer at stride 1 and 3 (computed once)."""
-    from cloud_port import CloudPortBackend
+    from ports import PortBackend
     rng = np.random.default_rng(40)
     shapes = [(375, 1242)] * 4
     gts = [C.depth_like(rng, 375, 1242, 2.0, 90.0) for _ in shapes]
@@ -40,7 +40,7 @@ def workload():
         g[rng.random(g.shape) < 0.5] = 0.0
     case = dict(pred=1.0 / np.stack([C.depth_like(rng, 192, 640, 1.0, 100.0) for _ in shapes]), shapes=shapes, gts=gts,
                 ratios=[1.1, 0.9, 1.0, 1.3], rgbs=C.colours(rng, shapes))
-    port = CloudPortBackend()
+    port = PortBackend()
     want = {}
     for stride in (1, 3):
         case["kw"] = dict(stride=stride, pred_is_disp=True, mask_gt=stride == 1, min_depth=1e-3, max_depth=80.0)
@@ -91,7 +91,7 @@ def test_evaluate_save_clouds_on_the_device(tmp_path, hip):
     """`evaluate(..., save_clouds=DIR)` on a synthetic KITTI split of saved disparities: the ground-truth files equal the
     host port's byte for byte, the prediction files equal a direct `ops.point_cloud` call on the device's own metrics
     rows (the ratio is read on the device), and the scores are those of a run without the flag."""
-    from cloud_port import CloudPortBackend
+    from ports import PortBackend
     from baseboostdepth_amd import evaluation, ops, pointcloud
     from baseboostdepth_amd.options import MonodepthOptions
     rng = np.random.default_rng(6)
@@ -110,7 +110,7 @@ def test_evaluate_save_clouds_on_the_device(tmp_path, hip):
     base = ["--eval_mono", "--eval_split", "eigen", "--splits_dir", str(tmp_path / "splits"), "--ext_disp_to_eval",
             str(tmp_path / "disps.npy")]
     mean_plain, _ = evaluation.evaluate(MonodepthOptions().parse(base), batch_size=3)
-    for where, kw in (("dev", {}), ("port", dict(backend=CloudPortBackend(), device="cpu"))):
+    for where, kw in (("dev", {}), ("port", dict(backend=PortBackend(), device="cpu"))):
         opt = MonodepthOptions().parse(base + ["--save_clouds", str(tmp_path / where), "--cloud_count", "4", "--cloud_stride", "2"])
         mean, _ = evaluation.evaluate(opt, batch_size=3, **kw)
         if where == "dev":

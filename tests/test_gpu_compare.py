@@ -27,8 +27,8 @@ def backend():
 
 @pytest.fixture(scope="module")
 def port():
-    from compare_port import ComparePortBackend
-    return ComparePortBackend()
+    from ports import PortBackend
+    return PortBackend()
 
 
 @pytest.fixture(scope="module")

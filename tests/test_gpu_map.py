@@ -25,8 +25,8 @@ def hip():
 
 @pytest.fixture(scope="module")
 def port():
-    from map_port import MapPortBackend
-    return MapPortBackend()
+    from ports import PortBackend
+    return PortBackend()
 
 
 @pytest.fixture(scope="module")

@@ -28,8 +28,8 @@ def v():
 
 @pytest.fixture(scope="module")
 def port():
-    from odom_port import OdomPortBackend
-    return OdomPortBackend()
+    from ports import PortBackend
+    return PortBackend()
 
 
 @pytest.mark.parametrize("case,L", oc.EVERY)

@@ -21,8 +21,8 @@ DEV = "cuda:0"
 
 @pytest.fixture(scope="module")
 def port():
-    from panel_port import PanelPortBackend
-    return PanelPortBackend()
+    from ports import PortBackend
+    return PortBackend()
 
 
 @pytest.fixture(scope="module")

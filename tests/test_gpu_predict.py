@@ -94,11 +94,11 @@ def test_tiny_ragged_batch_equals_the_host_port():
     """One call, an 8 x 8 network output for four images: one pixel; 15 and 35 pixels (fewer than a workgroup has
     threads, a last quad of three: byte stores); 480 pixels (two workgroups per histogram sweep, whole quads: packed
     stores).  Colours, floats and stats equal the host port's bit for bit."""
-    from viz_port import VizPortBackend
+    from ports import PortBackend
     from baseboostdepth_amd import ops
     disp = torch.rand(4, 1, 8, 8, generator=torch.Generator().manual_seed(31))
     colour, floats, stats = ops.disp_viz(disp.to(DEV), TINY_SIZES, want_float=True)
-    want_c, want_f, want_s = ops.disp_viz(disp, TINY_SIZES, want_float=True, backend=VizPortBackend())
+    want_c, want_f, want_s = ops.disp_viz(disp, TINY_SIZES, want_float=True, backend=PortBackend())
     assert np.array_equal(stats.cpu().numpy().view(np.uint32), want_s.numpy().view(np.uint32))
     for i, size in enumerate(TINY_SIZES):
         assert tuple(colour[i].shape) == size + (3,)

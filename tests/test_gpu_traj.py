@@ -27,8 +27,8 @@ GUARD = 12345.678
 
 @pytest.fixture(scope="module")
 def port():
-    from traj_port import TrajPortBackend
-    return TrajPortBackend()
+    from ports import PortBackend
+    return PortBackend()
 
 
 @pytest.mark.parametrize("name,mode", tc.EVERY)

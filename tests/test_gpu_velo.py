@@ -42,11 +42,11 @@ def test_one_ragged_launch_matches_the_reference(v, vel_depth):
 
 def test_device_equals_the_host_port_bit_for_bit(v):
     """Same header, same operation order: also where the reference is only matched to an ulp."""
-    from velo_port import VeloPortBackend
+    from ports import PortBackend
     from baseboostdepth_amd import ops
     for vel_depth in (True, False):
         dev_maps, _ = vc.run_batch(v, EVERY, vel_depth, ops.default_backend(), DEV)
-        host_maps, _ = vc.run_batch(v, EVERY, vel_depth, VeloPortBackend(), "cpu")
+        host_maps, _ = vc.run_batch(v, EVERY, vel_depth, PortBackend(), "cpu")
         for a, b in zip(dev_maps, host_maps):
             assert np.array_equal(vc.bits(a), vc.bits(b))
 

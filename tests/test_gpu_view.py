@@ -26,8 +26,8 @@ def hip():
 
 @pytest.fixture(scope="module")
 def port():
-    from view_port import ViewPortBackend
-    return ViewPortBackend()
+    from ports import PortBackend
+    return PortBackend()
 
 
 def _bg(name):

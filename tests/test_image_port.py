@@ -12,14 +12,14 @@ from PIL import Image
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from host_port import HostPortBackend  # noqa: E402
+from ports import PortBackend  # noqa: E402
 from oracle import loader_ref  # noqa: E402
 from baseboostdepth_amd import imageops  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def port():
-    return HostPortBackend()
+    return PortBackend()
 
 
 def _all_triples():

@@ -12,14 +12,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import image_checks  # noqa: E402
-from host_port import HostPortBackend  # noqa: E402
+from ports import PortBackend  # noqa: E402
 from oracle import loader_ref  # noqa: E402
 from baseboostdepth_amd import datasets  # noqa: E402
 
 
 @pytest.mark.parametrize("epoch,trimin,scales", [(3, True, [0, 1, 2, 3]), (12, True, [0]), (0, False, [0, 1, 2, 3])])
 def test_collated_batches_equal_reference_pipeline(tmp_path, epoch, trimin, scales):
-    image_checks.check_loader_batches(tmp_path, "cpu", HostPortBackend(), epoch, trimin, scales)
+    image_checks.check_loader_batches(tmp_path, "cpu", PortBackend(), epoch, trimin, scales)
 
 
 def test_frame_selection_matches_oracle_and_draw_order():
@@ -55,7 +55,7 @@ def test_stereo_sign_and_eval_items(tmp_path):
                                    is_train=False, kt=True, naive_mix=True)
     item = val[0]
     assert list(item["images"]) == [0] and not item["flip"] and not item["jitter"]
-    batch = datasets.DeviceCollate(64, 128, [0], "cpu", HostPortBackend())([val[0], val[1]])
+    batch = datasets.DeviceCollate(64, 128, [0], "cpu", PortBackend())([val[0], val[1]])
     assert batch[("color", 0, 0)].shape == (2, 3, 64, 128) and torch.equal(batch[("color", 0, 0)], batch[("color_aug", 0, 0)])
 
 
@@ -64,7 +64,7 @@ def test_worker_processes_with_shared_ring_equal_thread_pool(tmp_path):
     lines = image_checks.make_kitti_tree(str(tmp_path), frames=20)
     ds = datasets.KITTIRAWDataset(lines, 2, 64, 128, kt_path=str(tmp_path), rand=True, is_train=True, scales=[0, 1, 2, 3],
                                   kt=True, naive_mix=True, trimin=True, seed=3)
-    col = datasets.DeviceCollate(64, 128, [0, 1, 2, 3], "cpu", HostPortBackend())
+    col = datasets.DeviceCollate(64, 128, [0, 1, 2, 3], "cpu", PortBackend())
     a = list(datasets.DeviceLoader(ds, 4, col, num_workers=2, seed=1, workers="process"))
     b = list(datasets.DeviceLoader(ds, 4, col, num_workers=2, seed=1, workers="thread"))
     assert len(a) == len(b) == len(lines) // 4
@@ -91,7 +91,7 @@ def test_frame_cache_batches_equal_uncached_ones_and_decode_each_frame_once(tmp_
     def loader(cache, epoch):
         ds = datasets.KITTIRAWDataset(lines, epoch, H, W, kt_path=str(tmp_path), rand=True, is_train=True, scales=scales, kt=True,
                                       naive_mix=True, trimin=True, seed=3)
-        col = datasets.DeviceCollate(H, W, scales, "cpu", HostPortBackend(), cache=cache)
+        col = datasets.DeviceCollate(H, W, scales, "cpu", PortBackend(), cache=cache)
         return datasets.DeviceLoader(ds, 4, col, shuffle=True, drop_last=True, num_workers=2, seed=1, workers="thread")
 
     cache = datasets.FrameCache("cpu", capacity_mb << 20, scratch_bytes=64 << 20)

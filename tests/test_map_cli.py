@@ -1,5 +1,5 @@
 """CPU tier of `evaluate_pose.py --trajectory --save_map`: `evaluation.evaluate_pose` end to end through the host ports
-(tests/map_port.py) on a synthetic 12-frame sequence with injected stand-ins for the pose and depth networks and
+(tests/ports.py) on a synthetic 12-frame sequence with injected stand-ins for the pose and depth networks and
 ground-truth poses.  The written file must equal the numpy reference (tests/map_ref.py) computed from the same
 disparities and the returned aligned trajectory; without the flag nothing may differ."""
 import os
@@ -14,7 +14,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import map_checks as mc  # noqa: E402
 import map_ref as ref  # noqa: E402
-from map_port import MapPortBackend  # noqa: E402
+from ports import PortBackend  # noqa: E402
 from baseboostdepth_amd import evaluation, pointcloud  # noqa: E402
 from baseboostdepth_amd.options import MonodepthOptions  # noqa: E402
 
@@ -24,7 +24,7 @@ RampDepthDecoder, PassEncoder = mc.RampDepthDecoder, mc.PassEncoder
 
 @pytest.fixture(scope="module")
 def port():
-    return MapPortBackend()
+    return PortBackend()
 
 
 def _run(opt, loader, gt, port):

@@ -14,13 +14,13 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import map_checks as mc  # noqa: E402
 import map_ref as ref  # noqa: E402
-from map_port import MapPortBackend  # noqa: E402
+from ports import PortBackend  # noqa: E402
 from baseboostdepth_amd import _lib, ops, pointcloud  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def port():
-    return MapPortBackend()
+    return PortBackend()
 
 
 def test_the_reference_shows_the_cases_are_what_they_are_for():

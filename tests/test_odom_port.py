@@ -14,14 +14,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import odom_checks as oc  # noqa: E402
-from odom_port import OdomPortBackend  # noqa: E402
+from ports import PortBackend  # noqa: E402
 from baseboostdepth_amd import _lib, datasets, evaluation  # noqa: E402
 from baseboostdepth_amd.options import MonodepthOptions  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def port():
-    return OdomPortBackend()
+    return PortBackend()
 
 
 @pytest.fixture(scope="module")
@@ -129,8 +129,8 @@ def test_dataset_paths_and_line_parsing(tmp_path):
 
 
 def _image_port():
-    from host_port import HostPortBackend
-    return HostPortBackend()
+    from ports import PortBackend
+    return PortBackend()
 
 
 def test_windows_tables_and_trailing_drop(tmp_path):

@@ -15,7 +15,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import panel_checks as pc  # noqa: E402
 import panel_ref  # noqa: E402
-from panel_port import PanelPortBackend  # noqa: E402
+from ports import PortBackend  # noqa: E402
 from baseboostdepth_amd import _lib, ops  # noqa: E402
 from baseboostdepth_amd._lib import ptr  # noqa: E402
 from baseboostdepth_amd.plan import STEREO  # noqa: E402
@@ -23,7 +23,7 @@ from baseboostdepth_amd.plan import STEREO  # noqa: E402
 
 @pytest.fixture(scope="module")
 def port():
-    return PanelPortBackend()
+    return PortBackend()
 
 
 @pytest.fixture(scope="module")

@@ -14,14 +14,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import postproc_ref  # noqa: E402
-from postproc_port import PostprocPortBackend  # noqa: E402
+from ports import PortBackend  # noqa: E402
 from baseboostdepth_amd import _lib, ops  # noqa: E402
 from baseboostdepth_amd._lib import ptr  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def port():
-    return PostprocPortBackend()
+    return PortBackend()
 
 
 def test_shapes_cover_the_ramp_and_the_centre_column():

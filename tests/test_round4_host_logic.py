@@ -94,9 +94,9 @@ def test_combine_losses_equals_the_reference_arithmetic():
 def test_multi_scale_smoothness_equals_the_single_scale_node():
     """ops.normalised_smooth_losses (one launch pair for all scales) vs ops.normalised_smooth_loss per scale, through the
     host port of the kernels' arithmetic."""
-    import host_port
+    from ports import PortBackend
     from baseboostdepth_amd import ops
-    be = host_port.HostPortBackend()
+    be = PortBackend()
     g = torch.Generator().manual_seed(3)
     B, H, W = 3, 32, 64
     disps = [torch.rand(B, 1, H >> s, W >> s, generator=g).requires_grad_(True) for s in range(4)]

@@ -184,7 +184,7 @@ def test_structured_batch_registers_the_true_pose_warps():
     coherent: most backward tiles see a handful of live candidates, true-pose candidates win most pixels."""
     import types
     import torch.nn as nn
-    from host_port import HostPortBackend
+    from ports import PortBackend
     from baseboostdepth_amd.synthetic import (STRUCT_DISP, live_candidates_per_tile, structured_batch, structured_translation,
                                               synthetic_batch)
     from baseboostdepth_amd.trainer import Trainer
@@ -208,7 +208,7 @@ def test_structured_batch_registers_the_true_pose_warps():
                                        partial_skip=True, batched_pose=False, min_depth=0.1, max_depth=100.0, no_ssim=False,
                                        disparity_smoothness=1e-3, materialize_warps=False,
                                        frame_ids=sorted(inputs["frames"], key=lambda f: 99 if f == "s" else abs(f)))
-        tr.device, tr.backend, tr.num_scales = torch.device("cpu"), HostPortBackend(), 4
+        tr.device, tr.backend, tr.num_scales = torch.device("cpu"), PortBackend(), 4
         tr.models = {"pose_encoder": _Enc(), "pose": _Dec()}
         tr.valid_frames_trimin(inputs)
         out = tr.predict_poses(inputs)

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 import image_checks
-from host_port import HostPortBackend
+from ports import PortBackend
 from baseboostdepth_amd import datasets, steptables
 from baseboostdepth_amd.plan import get_plan
 
@@ -25,7 +25,7 @@ def _loader(lines, root, cache, epoch, train=True, seed=3):
     H, W, scales = 64, 128, [0, 1]
     ds = datasets.KITTIRAWDataset(lines, epoch, H, W, kt_path=root, rand=train, is_train=train, scales=scales, kt=True,
                                   naive_mix=True, trimin=True, seed=seed)
-    col = datasets.DeviceCollate(H, W, scales if train else [0], "cpu", HostPortBackend(), cache=cache)
+    col = datasets.DeviceCollate(H, W, scales if train else [0], "cpu", PortBackend(), cache=cache)
     return datasets.DeviceLoader(ds, 4, col, shuffle=train, drop_last=train, num_workers=2, seed=1, workers="thread")
 
 
@@ -66,7 +66,7 @@ def test_two_loaders_share_one_frame_cache_concurrently(tmp_path):
     gc.collect()
     assert not cache._held                                      # the collates are gone: their scratch areas are free again
     with pytest.raises(RuntimeError):                           # a third live collate on a two-region cache is refused
-        keep = [datasets.DeviceCollate(64, 128, [0], "cpu", HostPortBackend(), cache=cache) for _ in range(3)]
+        keep = [datasets.DeviceCollate(64, 128, [0], "cpu", PortBackend(), cache=cache) for _ in range(3)]
         del keep
 
 

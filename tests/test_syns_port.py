@@ -18,8 +18,8 @@ import syns_ref  # noqa: E402
 
 @pytest.fixture(scope="module")
 def be():
-    import syns_port
-    return syns_port.SynsPortBackend()
+    from ports import PortBackend
+    return PortBackend()
 
 
 def _set(gts, edges, crop=False):
@@ -240,12 +240,12 @@ def test_syns_dataset_paths_and_camera(tmp_path):
 def test_syns_items_go_through_the_device_collate(tmp_path):
     """Evaluation items of the SYNS dataset have the form DeviceCollate / DeviceLoader take (host port of the image
     kernels): frame 0 at the network's size, one row per item, in split order."""
-    from host_port import HostPortBackend
+    from ports import PortBackend
     from baseboostdepth_amd import datasets
     lines = C.make_syns_tree(str(tmp_path), 3)
     ds = datasets.SYNSRAWDataset(lines, 0, 32, 64, syns_path=str(tmp_path), is_train=False, naive_mix=True)
     assert len(ds) == 3 and ds[1]["images"][0].shape == (94, 310, 3)
-    loader = datasets.DeviceLoader(ds, 2, datasets.DeviceCollate(32, 64, [0], "cpu", HostPortBackend()), shuffle=False,
+    loader = datasets.DeviceLoader(ds, 2, datasets.DeviceCollate(32, 64, [0], "cpu", PortBackend()), shuffle=False,
                                    drop_last=False, num_workers=2)
     shapes = [b[("color", 0, 0)].shape for b in loader]
     assert shapes == [(2, 3, 32, 64), (1, 3, 32, 64)]

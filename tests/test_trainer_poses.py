@@ -10,14 +10,14 @@ import torch
 from fake_nets import FakePoseEncoder, fill_deterministic
 from fused_runner import bare_trainer, make_opt, compare_with_golden
 from golden_io import Case, POSE_CASES, GOLDEN_DIR
-from host_port import HostPortBackend
+from ports import PortBackend
 from pose_checks import check_pose_case
 from baseboostdepth_amd import networks
 
 
 @pytest.fixture(scope="module")
 def backend():
-    return HostPortBackend()
+    return PortBackend()
 
 
 def _fkey(f):

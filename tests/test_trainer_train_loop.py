@@ -6,7 +6,7 @@ import os
 
 import torch
 
-from host_port import HostPortBackend
+from ports import PortBackend
 from baseboostdepth_amd import Trainer, synthetic
 from baseboostdepth_amd.options import MonodepthOptions
 
@@ -26,7 +26,7 @@ def test_train_saves_checkpoints_and_resumes(tmp_path):
     torch.manual_seed(0)
     torch.set_num_threads(4)
     opts = _opts(str(tmp_path))
-    tr = Trainer(opts, backend=HostPortBackend())
+    tr = Trainer(opts, backend=PortBackend())
     tr.train(_loader(opts))
     folder = os.path.join(str(tmp_path), "t", "models", "weights_0")
     for name in ("encoder", "depth", "pose_encoder", "pose", "adam"):
@@ -39,7 +39,7 @@ def test_train_saves_checkpoints_and_resumes(tmp_path):
     # resume: weights_0 -> epoch 1; scheduler fast-forwarded by one step; weights identical to the saved ones
     opts2 = _opts(str(tmp_path), "--load_weights_folder %s" % folder)
     opts2.num_epochs = 2
-    tr2 = Trainer(opts2, backend=HostPortBackend())
+    tr2 = Trainer(opts2, backend=PortBackend())
     assert tr2.resume_epoch() == 1
     for k, v in tr.models["depth"].state_dict().items():
         assert torch.equal(v, tr2.models["depth"].state_dict()[k]), k
@@ -66,7 +66,7 @@ def test_vit_process_batch_on_cpu_host_port():
     torch.set_num_threads(4)
     o = MonodepthOptions().parse(("--ViT --no_cuda --weights_init scratch --height %d --width %d --batch_size %d"
                                   % (H, W, B)).split())
-    tr = Trainer(o, backend=HostPortBackend())
+    tr = Trainer(o, backend=PortBackend())
     tr.set_train()
     batch = synthetic.synthetic_batch([1] * B, H, W, o.scales, device="cpu", seed=1)
     before = [p.detach().clone() for p in tr.models["encoder"].parameters()]
@@ -82,7 +82,7 @@ def test_capture_warm_up_steps_issue_no_collective():
     torch.set_num_threads(4)
     o = MonodepthOptions().parse(("--no_cuda --weights_init scratch --height %d --width %d --batch_size %d"
                                   % (H, W, B)).split())
-    tr = Trainer(o, backend=HostPortBackend())
+    tr = Trainer(o, backend=PortBackend())
     tr.set_train()
     calls = []
     tr.grad_sync = lambda: calls.append(1)

@@ -13,7 +13,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import panel_checks as pc  # noqa: E402
 import panel_ref  # noqa: E402
-from panel_port import PanelPortBackend  # noqa: E402
+from ports import PortBackend  # noqa: E402
 from baseboostdepth_amd import Trainer, ops, synthetic  # noqa: E402
 from baseboostdepth_amd.options import MonodepthOptions  # noqa: E402
 from baseboostdepth_amd.trainlog import ARGMIN_KEYS, TrainLog, argmin_fractions, sec_to_hm_str  # noqa: E402
@@ -26,7 +26,7 @@ REFERENCE_LINE = ("epoch {:>3} | batch {:>6} | examples/s: {:5.1f}" +
 
 @pytest.fixture(scope="module")
 def port():
-    return PanelPortBackend()
+    return PortBackend()
 
 
 def _hm(t):

@@ -17,14 +17,14 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import traj_checks as tc  # noqa: E402
 import traj_ref as ref  # noqa: E402
-from traj_port import TrajPortBackend  # noqa: E402
+from ports import PortBackend  # noqa: E402
 from baseboostdepth_amd import _lib, evaluation  # noqa: E402
 from baseboostdepth_amd.options import MonodepthOptions  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def port():
-    return TrajPortBackend()
+    return PortBackend()
 
 
 def test_the_reference_takes_the_branches_the_cases_are_there_for():

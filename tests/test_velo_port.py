@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import velo_checks as vc  # noqa: E402
-from velo_port import VeloPortBackend  # noqa: E402
+from ports import PortBackend  # noqa: E402
 from baseboostdepth_amd import kitti_utils, ops  # noqa: E402
 from baseboostdepth_amd.evaluation import GroundTruthSet  # noqa: E402
 
@@ -21,7 +21,7 @@ EVERY = [(c, cam) for c in vc.CASES for cam in vc.CAMS]
 
 @pytest.fixture(scope="module")
 def port():
-    return VeloPortBackend()
+    return PortBackend()
 
 
 @pytest.fixture(scope="module")

@@ -1,5 +1,5 @@
 """CPU tier of the picture command lines: `evaluate_pose.py --trajectory --save_plot` end to end through the host ports
-(tests/view_port.py) on the synthetic 12-frame sequence of tests/map_checks.py, and `test_simple.py --point_cloud
+(tests/ports.py) on the synthetic 12-frame sequence of tests/map_checks.py, and `test_simple.py --point_cloud
 --cloud_view` with a stub predictor.  The written pictures must decode to what the numpy reference (tests/view_ref.py)
 draws from the same run's trajectories, voxels and clouds, with a layout worked out here from the documented rules;
 without the flags nothing may differ."""
@@ -26,8 +26,8 @@ GT, PRED, START, BAR = (40, 40, 40), (214, 39, 40), (31, 119, 180), (0, 0, 0)
 
 @pytest.fixture(scope="module")
 def port():
-    from view_port import ViewPortBackend
-    return ViewPortBackend()
+    from ports import PortBackend
+    return PortBackend()
 
 
 def _run(opt, loader, gt, port):

@@ -20,8 +20,8 @@ H, W = vc.H, vc.W
 
 @pytest.fixture(scope="module")
 def port():
-    from view_port import ViewPortBackend
-    return ViewPortBackend()
+    from ports import PortBackend
+    return PortBackend()
 
 
 @pytest.fixture(scope="module")

@@ -12,13 +12,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import viz_checks  # noqa: E402
-from viz_port import VizPortBackend  # noqa: E402
+from ports import PortBackend  # noqa: E402
 from baseboostdepth_amd import ops  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def port():
-    return VizPortBackend()
+    return PortBackend()
 
 
 @pytest.fixture(scope="module")
