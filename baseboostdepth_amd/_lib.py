@@ -20,7 +20,7 @@ PROJ_STRIDE = 24
 KIND_WARP, KIND_IDENT, FLAG_NO_POSE_GRAD = 0, 1, 0x100
 COMPOSE_STRIDE, COMPOSE_ERROR, COMPOSE_REPLACE = 12, 1, 2
 PAIR_SHIFT = 16        # bits 16-23 of bbd_cand_t.kind: 1 + index of the pass partner (hint), 0 = none
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 _p = ctypes.c_void_p
 _i = ctypes.c_int
@@ -74,6 +74,8 @@ SIGNATURES = {
     "bbd_syns_pointcloud": [_p] * 6 + [_i, _p] + [_i] * 6 + [_d] * 5 + [_i, _p],
     "bbd_point_cloud_scratch_ints": [_i, _i, _i, _i],
     "bbd_point_cloud": [_p] * 10 + [_i] * 7 + [_d] * 5 + [_i, _p],
+    "bbd_ground_scale_scratch_floats": [_i, _i, _i],
+    "bbd_ground_scale": [_p] * 5 + [_i, _i, _i, _d, _d, _i, _i, _p],
     "bbd_map_state_bytes": [_i],
     "bbd_map_finish_scratch_ints": [_i],
     "bbd_map_clear": [_p] * 4 + [_i, _p],
@@ -234,6 +236,9 @@ class HipLibrary:
 
     def point_cloud_scratch_ints(self, n, max_h, max_w, stride):
         return self._dll.bbd_point_cloud_scratch_ints(n, max_h, max_w, stride)
+
+    def ground_scale_scratch_floats(self, n, h, w):
+        return self._dll.bbd_ground_scale_scratch_floats(n, h, w)
 
     def map_state_bytes(self, T):
         return self._dll.bbd_map_state_bytes(T)

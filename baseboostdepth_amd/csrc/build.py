@@ -36,6 +36,7 @@ SRCS = _here("""
     bbd_panel.hip
     bbd_compare.hip
     bbd_cloud.hip
+    bbd_ground.hip
     bbd_map.hip
     bbd_view.hip
 """)

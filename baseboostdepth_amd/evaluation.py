@@ -315,6 +315,13 @@ def evaluate(opt, dataloader=None, gt_depths=None, models=None, batch_size=16, g
     intrinsics at the ground-truth size, SYNS the dataset's; `cloud_rays` ("pixel" | "reference") chooses the pairing of
     pixels and rays (`pointcloud_metrics`).  It needs the metrics rows, so it is refused together with `no_eval`.
 
+    `scale_recovery` ("median" | "ground"): under "ground" a KITTI mono prediction is scaled without
+    ground truth - every batch goes through `ops.ground_scale` with the KITTI intrinsics of the prediction's own size
+    (`camera_height` 1.65, `ground_angle` 5.0), its disparities are divided on the device by the scale of their image
+    and scored without median scaling; `save_clouds` exports those scaled disparities.  The ratios line and the
+    returned ratios are the recovered scales; an image without ground has a NaN scale, is named in a warning and left
+    out of the mean.  Refused with `eval_stereo`, `disable_median_scaling` and the SYNS split.
+
     `backend` and `device` are for tests (the host ports); by default the HIP backend and `cuda:<opt.cuda>`."""
     from . import tuning
     tuning.use_shipped_db()      # (no Trainer is built here: the tuned MIOpen database is wired explicitly)
@@ -327,6 +334,7 @@ def evaluate(opt, dataloader=None, gt_depths=None, models=None, batch_size=16, g
     ext = getattr(opt, "ext_disp_to_eval", None)
     no_eval = bool(getattr(opt, "no_eval", False))
     clouds = _CloudSaver.from_options(opt, no_eval, backend)             # raises before any prediction
+    _ground_options(opt)                                                 # as well
     split_dir = os.path.join(getattr(opt, "splits_dir", "splits"), opt.eval_split)
     syns = opt.eval_split == "SYNS"
 
@@ -496,6 +504,40 @@ class _CloudSaver:
             print("-> Saved {:d} point clouds to {}".format(len(self.written), self.folder))
 
 
+def _ground_options(opt):
+    """`scale_recovery == "ground"` -> the keywords of `ops.ground_scale`; "median" (or an `opt` without the field) ->
+    None.  What the scale would collide with is refused."""
+    mode = getattr(opt, "scale_recovery", "median")
+    if mode == "median":
+        return None
+    if mode != "ground":
+        raise ValueError("scale_recovery is median or ground, got %r" % (mode,))
+    for name, set_ in (("eval_stereo", opt.eval_stereo), ("disable_median_scaling", opt.disable_median_scaling),
+                       ("eval_split SYNS", opt.eval_split == "SYNS")):
+        if set_:
+            raise ValueError("scale_recovery ground scales a mono prediction on a KITTI split by the camera's height "
+                             "above the road: it excludes %s" % name)
+    return dict(camera_height=float(getattr(opt, "camera_height", 1.65)), angle_deg=float(getattr(opt, "ground_angle", 5.0)))
+
+
+def _ground_summary(rows, ground_rows):
+    """The printed summary and the result of a split scored under `scale_recovery ground`: the mean over the images
+    that have a scale - the others are counted and named - and the ratios line from the ground rows."""
+    ratios = ground_rows[:, 7]
+    found = np.isfinite(ratios)
+    if not found.all():
+        lost = np.nonzero(~found)[0]
+        print("   WARNING: no ground found in {:d} of {:d} images, left out of the mean: {}".format(
+            len(lost), len(ratios), ", ".join(str(i) for i in lost)))
+    if found.any():
+        med = np.median(ratios[found])
+        print(" Scaling ratios | med: {:0.3f} | std: {:0.3f}".format(med, np.std(ratios[found] / med)))
+    mean_errors = rows[found, :7].mean(0) if found.any() else np.full(7, np.nan)
+    print("\n  " + ("{:>8} | " * 7).format("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3"))
+    print(("&{: 8.3f}  " * 7).format(*mean_errors.tolist()) + "\\\\")
+    return mean_errors, ratios
+
+
 def _evaluate_kitti(opt, source, save_path, no_eval, gt_depths, split_dir, device, backend=None, clouds=None):
     """The KITTI splits: every batch of `source` is scored by one `bbd_depth_metrics` launch while it is in HBM."""
     import os
@@ -518,12 +560,21 @@ def _evaluate_kitti(opt, source, save_path, no_eval, gt_depths, split_dir, devic
     scale = opt.pred_depth_scale_factor
     if opt.eval_stereo:                                   # evaluate_depth.py:233-237
         median_scaling, scale = False, STEREO_SCALE_FACTOR
-    rows, kept, first = [], [], 0
+    ground = _ground_options(opt)
+    if ground is not None:                                # the scale comes from the ground rows: nothing else scales
+        median_scaling, scale = False, 1
+    rows, ground_rows, kept, first = [], [], [], 0
     with torch.no_grad():
         for pred_disp in source:
             n = pred_disp.shape[0]
             if save_path is not None:
                 kept.append(pred_disp)
+            if ground is not None:
+                from . import pointcloud
+                ground_rows.append(ops.ground_scale(pred_disp, pointcloud.intrinsics(*pred_disp.shape[-2:]),
+                                                    pred_is_disp=True, backend=backend, **ground)[0])
+                # metres = scale / disparity: the disparities are divided by the scale, a NaN scale leaves NaNs
+                pred_disp = pred_disp / ground_rows[-1][:, 7].view([n] + [1] * (pred_disp.dim() - 1))
             rows.append(depth_metrics(pred_disp, gts, list(range(first, first + n)), min_depth=1e-3, max_depth=80.0,
                                       pred_is_disp=True, median="numpy", median_scaling=median_scaling,
                                       scale_factor=scale, backend=backend))
@@ -534,8 +585,13 @@ def _evaluate_kitti(opt, source, save_path, no_eval, gt_depths, split_dir, devic
         _save_disps(kept, save_path)
     if clouds is not None:
         clouds.done()
-    rows = torch.cat(rows).cpu().numpy().astype(np.float64)          # the only host synchronisation of the scoring
+    rows = torch.cat(rows)
+    if ground is not None:                                # the ground rows travel with the metrics rows
+        rows = torch.cat([rows, torch.cat(ground_rows)], 1)
+    rows = rows.cpu().numpy().astype(np.float64)                     # the only host synchronisation of the scoring
     assert first == len(gts), "split has %d images, ground truth %d" % (first, len(gts))
+    if ground is not None:
+        return _ground_summary(rows[:, :EVAL_OUT], rows[:, EVAL_OUT:])
     mean_errors = rows[:, :7].mean(0)
     ratios = rows[:, 7] if median_scaling else None
     if median_scaling:

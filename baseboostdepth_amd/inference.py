@@ -148,8 +148,51 @@ class DepthPredictor:
             off += ops.viz_granule(npx)
         return results
 
+    def _scaled_disparity(self, images, post_process):
+        """(uploaded images, the scaled disparity min_disp + (max_disp - min_disp) * disp at network size [n,.,h,w])."""
+        self.encoder.eval()
+        self.decoder.eval()
+        src, jobs = self.upload(images)
+        x = self.prepare_uploaded(src, jobs)
+        if post_process:
+            disp = ops.post_process_disp(self.disparity(torch.cat((x, torch.flip(x, [3])), 0)), self.backend)
+        else:
+            disp = self.disparity(x)
+        self.last_disp = disp
+        min_disp, max_disp = 1.0 / self.max_depth, 1.0 / self.min_depth
+        return src, min_disp + (max_disp - min_disp) * disp
+
+    def _ground_rows(self, scaled, sizes, inv_K, camera_height, angle_deg, want_mask):
+        """`ops.ground_scale` of scaled disparities at network size, with the intrinsics of every image (`inv_K` [3,3] or
+        one per image, for the image's own size) brought to the network's map (`pointcloud.intrinsics_at`)."""
+        inv_K = np.asarray(inv_K, np.float32)
+        inv_K = inv_K[None].repeat(len(sizes), 0) if inv_K.ndim == 2 else inv_K
+        at_map = np.stack([pointcloud.intrinsics_at(k, size, scaled.shape[-2:]) for k, size in zip(inv_K, sizes)])
+        return ops.ground_scale(scaled, at_map, camera_height=camera_height, angle_deg=angle_deg, pred_is_disp=True,
+                                want_mask=want_mask, backend=self.backend)
+
+    def ground_scale(self, images, inv_K=None, camera_height=1.65, angle_deg=5.0, post_process=False, want_mask=False):
+        """The metric scale of every image's prediction from the height of the camera above the road
+        (`ops.ground_scale` on the scaled disparity at network size): float32 [n, 12] host rows - [0] the median
+        ground height in the prediction's units, [1] ground pixels, [2] candidates, [7] the scale: metres = scale /
+        scaled disparity, NaN where no ground was found - and, with `want_mask`, (rows, masks) with masks uint8
+        [n, feed_h, feed_w] (1 = ground).  `inv_K` as `predict_cloud` takes it."""
+        if not len(images):
+            return (np.zeros((0, 12), np.float32), np.zeros((0, self.feed_height, self.feed_width), np.uint8)) \
+                if want_mask else np.zeros((0, 12), np.float32)
+        sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
+        if inv_K is None:
+            inv_K = np.stack([pointcloud.intrinsics(H0, W0) for H0, W0 in sizes])
+        with torch.no_grad():
+            _, scaled = self._scaled_disparity(images, post_process)
+            rows, mask = self._ground_rows(scaled, sizes, inv_K, camera_height, angle_deg, want_mask)
+            host = [_to_host(rows)] + ([_to_host(mask)] if want_mask else [])
+            if self.device.type == "cuda":
+                torch.cuda.current_stream(self.device).synchronize()
+        return (host[0].numpy(), host[1].numpy()) if want_mask else host[0].numpy()
+
     def predict_cloud(self, images, inv_K=None, scale=1.0, max_depth=None, stride=1, post_process=False, view=None,
-                      view_size=3):
+                      view_size=3, camera_height=None, angle_deg=5.0, ground_mask=False):
         """The coloured point cloud of every image: one structured array (`pointcloud.VERTEX_DTYPE`: x, y, z, red,
         green, blue, alpha) per image, ready for `pointcloud.write_ply`.  The same network pass as `predict`; the
         scaled disparity min_disp + (max_disp - min_disp) * disp at network size goes through ONE `ops.point_cloud`
@@ -162,33 +205,48 @@ class DepthPredictor:
 
         `view=(yaw, pitch)` in degrees also draws every cloud as its camera sees it after a turn about the point on
         the optical axis at the cloud's median depth (`cloud_views`), every point a square of `view_size` pixels, and
-        returns (clouds, pictures): one uint8 [H,W,3] array per image, at the image's size."""
+        returns (clouds, pictures): one uint8 [H,W,3] array per image, at the image's size.
+
+        `camera_height` (metres; `scale` must then be 1) makes the clouds metric without ground truth: the scaled
+        disparity goes through `ops.ground_scale` (normals within `angle_deg` of the down axis) and its rows, still on
+        the device, are the per-image ratio of the export; the default far limit is then 80.0, and an image without
+        ground has a NaN ratio and an empty cloud.  The result then ends in one more element, the ground record: a
+        dict of `rows` (float32 [n,12] on the host, as `ground_scale` returns them) and `masks` (uint8 [n, feed_h,
+        feed_w] with `ground_mask`, else None)."""
+        if camera_height is not None and scale != 1.0:
+            raise ValueError("predict_cloud: camera_height recovers the scale, so scale must be 1.0, got %r" % (scale,))
         if not len(images):
-            return [] if view is None else ([], [])
+            out = ([],) + (([],) if view is not None else ()) + \
+                ((dict(rows=np.zeros((0, 12), np.float32), masks=None),) if camera_height is not None else ())
+            return out[0] if len(out) == 1 else out
         sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
         if inv_K is None:
             inv_K = np.stack([pointcloud.intrinsics(H0, W0) for H0, W0 in sizes])
-        far = self.max_depth * scale if max_depth is None else float(max_depth)
+        if max_depth is not None:
+            far = float(max_depth)
+        else:
+            far = 80.0 if camera_height is not None else self.max_depth * scale
         with torch.no_grad():
-            self.encoder.eval()
-            self.decoder.eval()
-            src, jobs = self.upload(images)
-            x = self.prepare_uploaded(src, jobs)
-            if post_process:
-                disp = ops.post_process_disp(self.disparity(torch.cat((x, torch.flip(x, [3])), 0)), self.backend)
-            else:
-                disp = self.disparity(x)
-            self.last_disp = disp
-            min_disp, max_disp = 1.0 / self.max_depth, 1.0 / self.min_depth
-            scaled = min_disp + (max_disp - min_disp) * disp
+            src, scaled = self._scaled_disparity(images, post_process)
+            rows = mask = None
+            if camera_height is not None:
+                rows, mask = self._ground_rows(scaled, sizes, inv_K, camera_height, angle_deg, ground_mask)
             # `upload` packs the images back to back: image i's bytes start at 3x its pixel offset
-            cloud = ops.point_cloud(scaled, ops.cloud_rows(sizes), inv_K, rgb=src, stride=stride,
+            cloud = ops.point_cloud(scaled, ops.cloud_rows(sizes), inv_K, rows=rows, rgb=src, stride=stride,
                                     min_depth=0.0, max_depth=far, pred_is_disp=True,
                                     scale_factor=scale, backend=self.backend)
+            ground = None
+            if rows is not None:                           # queued before the cloud's read-back synchronises the stream
+                ground = [_to_host(rows)] + ([_to_host(mask)] if mask is not None else [])
             clouds = pointcloud.cloud_arrays(*cloud)
-            if view is None:
-                return clouds
-            return clouds, cloud_views(cloud, clouds, sizes, inv_K, view, view_size, self.backend)
+            out = (clouds,)
+            if view is not None:
+                out += (cloud_views(cloud, clouds, sizes, inv_K, view, view_size, self.backend),)
+            if ground is not None:
+                if self.device.type == "cuda":
+                    torch.cuda.current_stream(self.device).synchronize()
+                out += (dict(rows=ground[0].numpy(), masks=ground[1].numpy() if len(ground) > 1 else None),)
+            return out[0] if len(out) == 1 else out
 
 
 def cloud_views(cloud, clouds, sizes, inv_K, view, size=3, backend=None):
@@ -247,6 +305,16 @@ def parse_args(argv=None):
                              "by these degrees about the point at the median depth on its optical axis")
     parser.add_argument("--cloud_view_size", type=int, default=3, choices=[1, 3, 5, 7],
                         help="side of a point's square in the view, in pixels")
+    parser.add_argument("--camera_height", type=float, default=None, metavar="METRES",
+                        help="with --point_cloud: the height of the camera above the road; the cloud is brought to "
+                             "metres by the median height of the pixels found to be ground (no ground truth needed; "
+                             "1.65 for KITTI).  Replaces --cloud_scale")
+    parser.add_argument("--ground_angle", type=float, default=5.0, metavar="DEG",
+                        help="with --camera_height: a pixel is ground when its surface normal lies within this angle "
+                             "of the camera's down axis")
+    parser.add_argument("--ground_mask", action="store_true",
+                        help="with --camera_height: also write <name>_Base_ground.png, the ground pixels at network "
+                             "size (0 and 255)")
     camera = parser.add_mutually_exclusive_group()
     camera.add_argument("--fov", type=float, default=None, metavar="DEG",
                         help="horizontal field of view of the camera in degrees (default: the KITTI intrinsics)")
@@ -261,6 +329,17 @@ def parse_args(argv=None):
         parser.error("--cloud_scale must be positive")
     if args.cloud_view is not None and not args.point_cloud:
         parser.error("--cloud_view needs --point_cloud")
+    if args.camera_height is not None:
+        if not args.point_cloud:
+            parser.error("--camera_height needs --point_cloud")
+        if not args.camera_height > 0:
+            parser.error("--camera_height must be positive")
+        if args.cloud_scale != 1.0:
+            parser.error("--camera_height recovers the scale from the ground: it excludes a --cloud_scale other than 1.0")
+    elif args.ground_mask:
+        parser.error("--ground_mask needs --camera_height")
+    if not 0.0 <= args.ground_angle < 90.0:
+        parser.error("--ground_angle must lie in [0, 90) degrees")
     return args
 
 
@@ -305,6 +384,32 @@ def _save_view(out_dir, path, picture):
     return dest
 
 
+def _save_ground(out_dir, path, mask):
+    import PIL.Image as pil
+    stem = os.path.splitext(os.path.basename(path))[0]
+    dest = os.path.join(out_dir, "{}_Base_ground.png".format(stem))
+    pil.fromarray(np.asarray(mask, np.uint8) * np.uint8(255)).save(dest)
+    return dest
+
+
+def _report_ground(pool, out_dir, paths, ground):
+    """One line per image from the ground record of `predict_cloud`, a warning where no ground was found; returns the
+    futures of the mask files, where the record holds masks."""
+    saves = []
+    for i, path in enumerate(paths):
+        median, count, candidates, scale = (float(ground["rows"][i][c]) for c in (0, 1, 2, 7))
+        name = os.path.basename(path)
+        if np.isnan(scale):
+            print("   WARNING: {}: no ground found ({:d} ground pixels of {:d} candidates); the cloud is left empty"
+                  .format(name, int(count), int(candidates)))
+        else:
+            print("   {}: scale {:.4f} | median ground height {:.4f} | ground {:.1f}% of {:d} candidates"
+                  .format(name, scale, median, 100.0 * count / max(candidates, 1.0), int(candidates)))
+        if ground.get("masks") is not None:
+            saves.append(pool.submit(_save_ground, out_dir, path, ground["masks"][i]))
+    return saves
+
+
 def _cloud_inv_K(args, images):
     return np.stack([pointcloud.intrinsics(im.shape[0], im.shape[1], fov=getattr(args, "fov", None),
                                            fxfycxcy=getattr(args, "intrinsics", None)) for im in images])
@@ -314,6 +419,9 @@ def run_cli(args, predictor=None):
     """Body of test_simple.py.  `predictor` may be injected (tests); by default it is loaded from `args.weights`.
     With `--point_cloud` every batch also goes through `predict_cloud` (a second network pass: `predict` is left as it
     is) and `<name>_Base.ply` is written next to the JPEG; `--cloud_view YAW PITCH` adds `<name>_Base_view.png`.
+    `--camera_height METRES` scales every cloud by the camera's height above its ground pixels (`ops.ground_scale`),
+    prints the scale, the median ground height and the ground share of every image - a warning where no ground was
+    found - and, with `--ground_mask`, writes `<name>_Base_ground.png`.
     Returns the list of written JPEG paths."""
     paths, out_dir = find_inputs(args.image_path, args.save_path, args.ext)
     if predictor is None:
@@ -340,12 +448,19 @@ def run_cli(args, predictor=None):
             if getattr(args, "point_cloud", False):
                 kw = dict(inv_K=_cloud_inv_K(args, images), scale=args.cloud_scale, max_depth=args.cloud_max_depth,
                           stride=args.cloud_stride, post_process=bool(getattr(args, "post_process", False)))
-                if getattr(args, "cloud_view", None) is not None:        # as above: the keyword only when it is set
-                    clouds, pictures = predictor.predict_cloud(images, view=tuple(args.cloud_view),
-                                                               view_size=getattr(args, "cloud_view_size", 3), **kw)
-                    cloud_saves += [pool.submit(_save_view, out_dir, p, v) for p, v in zip(chunk, pictures)]
-                else:
-                    clouds = predictor.predict_cloud(images, **kw)
+                if getattr(args, "cloud_view", None) is not None:        # as above: the keywords only when they are set
+                    kw.update(view=tuple(args.cloud_view), view_size=getattr(args, "cloud_view_size", 3))
+                camera_height = getattr(args, "camera_height", None)
+                if camera_height is not None:
+                    kw.update(camera_height=camera_height, angle_deg=getattr(args, "ground_angle", 5.0),
+                              ground_mask=bool(getattr(args, "ground_mask", False)))
+                result = predictor.predict_cloud(images, **kw)
+                result = result if isinstance(result, tuple) else (result,)
+                clouds = result[0]
+                if "view" in kw:
+                    cloud_saves += [pool.submit(_save_view, out_dir, p, v) for p, v in zip(chunk, result[1])]
+                if camera_height is not None:
+                    cloud_saves += _report_ground(pool, out_dir, chunk, result[-1])
                 cloud_saves += [pool.submit(_save_cloud, out_dir, p, c) for p, c in zip(chunk, clouds)]
         written = [f.result() for f in pending]
         for f in cloud_saves:

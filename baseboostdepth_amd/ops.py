@@ -1816,6 +1816,51 @@ def point_cloud(pred, rows_desc, inv_K, gt=None, rows=None, rgb=None, stride=1, 
     return out, counts, regions
 
 
+# ---------------------------------------------------------------------------- metric scale from the ground plane
+def ground_scale(pred, inv_K, camera_height=1.65, angle_deg=5.0, pred_is_disp=False, min_count=64, want_mask=False,
+                 backend=None):
+    """The factor that brings every map of `pred` ([n,1,h,w] or [n,h,w], depth or - `pred_is_disp` - disparity of unknown
+    scale) to metres, from the height of the camera above the road, in ONE `bbd_ground_scale` call (two launches, nothing
+    read back).  Pixels are back-projected through `inv_K` ([3,3], [4,4] or one per image, on the host or the device;
+    for pixels of the h x w map itself: `pointcloud.intrinsics_at`); those whose surface normal lies within `angle_deg`
+    of the camera's down axis and that lie below the camera are ground, and the scale is `camera_height` over the median
+    distance of their tangent planes from the camera.
+
+    Returns (rows, mask): rows float32 [n, EVAL_OUT] on the device - [0] that median, [1] the number of ground pixels,
+    [2] the number of candidates (interior pixels with nine valid depths), [7] the scale, in the slot `point_cloud`
+    reads as `rows[i][7]`; [0] and [7] are NaN for an image with fewer than max(min_count, 1) ground pixels - and, with
+    `want_mask`, uint8 [n,h,w] (1 = ground), else None."""
+    import math
+    backend = backend or default_backend()
+    pred = pred.detach()
+    if pred.dim() == 4:
+        assert pred.shape[1] == 1
+        pred = pred[:, 0]
+    assert pred.dim() == 3 and pred.shape[0] > 0
+    pred = pred.contiguous().float()
+    n, h, w = pred.shape
+    dev = pred.device
+    if torch.is_tensor(inv_K):
+        iK = inv_K.detach().to(torch.float32)
+    else:
+        iK = torch.as_tensor(np.asarray(inv_K, dtype=np.float32))
+    iK = iK[..., :3, :3].expand(n, 3, 3) if iK.dim() == 2 else iK[:, :3, :3]
+    assert tuple(iK.shape) == (n, 3, 3)
+    iK = iK.contiguous() if iK.device == dev else upload(iK.contiguous(), dev)
+    n_floats = backend.lib.ground_scale_scratch_floats(n, h, w)
+    if n_floats < 0:
+        raise _lib.BbdError("ground_scale: %d maps of %d x %d pixels are more than one call holds; split the batch"
+                            % (n, h, w))
+    backend._check(pred, iK)
+    rows = torch.empty(n, _lib.EVAL_OUT, dtype=torch.float32, device=dev)
+    mask = torch.empty(n, h, w, dtype=torch.uint8, device=dev) if want_mask else None
+    scratch = torch.empty(n_floats, dtype=torch.float32, device=dev)
+    backend.run("bbd_ground_scale", pred, ptr(pred), ptr(iK), ptr(rows), ptr(mask), ptr(scratch), n, h, w,
+                float(camera_height), math.cos(math.radians(float(angle_deg))), int(min_count),
+                _lib.EVAL_PRED_IS_DISP if pred_is_disp else 0)
+    return rows, mask
+
+
 # ---------------------------------------------------------------------------- scene map (voxel fusion)
 MapState = collections.namedtuple("MapState", "keys pos col counters T")
 MapState.__doc__ = """The caller-owned state of the `bbd_map_*` entries for a table of T slots: `keys` int64 [T] (the

@@ -67,6 +67,10 @@ _FLAGS = [
     ("--save_clouds", dict(type=str, default=None, metavar="DIR")), ("--cloud_count", dict(type=int, default=8)),
     ("--cloud_stride", dict(type=int, default=1)),
     ("--cloud_rays", dict(type=str, default="pixel", choices=["pixel", "reference"])),
+    # evaluate_depth.py: where the scale of a mono prediction comes from - the LiDAR median of every image (the
+    # reference), or the camera's height above the pixels found to be road, without ground truth
+    ("--scale_recovery", dict(type=str, default="median", choices=["median", "ground"])),
+    ("--camera_height", dict(type=float, default=1.65)), ("--ground_angle", dict(type=float, default=5.0)),
 ]
 # other zoos / datasets of the reference: parsed, refused when set
 _OUT_OF_SCOPE = ["--SYNS_eval", "--SQL", "--SQL_L", "--CA_depth", "--DIFFNet", "--stereo_guide",
@@ -132,6 +136,15 @@ class MonodepthOptions:
                                   "of each image's metrics row, and --no_eval produces no metrics rows")
             if self.options.cloud_count < 1 or self.options.cloud_stride < 1:
                 self.parser.error("--cloud_count and --cloud_stride must be at least 1")
+        if self.options.scale_recovery == "ground":
+            for flag, set_ in (("--eval_stereo", self.options.eval_stereo),
+                               ("--disable_median_scaling", self.options.disable_median_scaling),
+                               ("--eval_split SYNS", self.options.eval_split == "SYNS")):
+                if set_:
+                    self.parser.error("--scale_recovery ground scales a mono prediction on a KITTI split by the camera's "
+                                      "height above the road: it excludes %s" % flag)
+            if not self.options.camera_height > 0 or not 0.0 <= self.options.ground_angle < 90.0:
+                self.parser.error("--camera_height must be positive and --ground_angle lie in [0, 90) degrees")
         if self.options.rand and not self.options.no_step_graph:
             self.options.step_graph = True
         if self.options.early_pose_rows != "max":

@@ -71,6 +71,22 @@ def intrinsics(H, W, K=None, fov=None, fxfycxcy=None):
     return np.ascontiguousarray(np.linalg.pinv(camera_matrix(H, W, K, fov, fxfycxcy))[:3, :3].astype(np.float32))
 
 
+def intrinsics_at(inv_K, size, map_size):
+    """float32 [3,3] inverse intrinsics for pixels of an h x w map (`map_size`) of the same view, from those of the
+    H0 x W0 image (`size`; `inv_K` [3,3] or [4,4]): inv_K . A with A = [[sx, 0, 0.5 sx - 0.5], [0, sy, 0.5 sy - 0.5],
+    [0, 0, 1]], sx = W0 / w, sy = H0 / h - map pixel (x, y) lies at image position ((x + 0.5) sx - 0.5, (y + 0.5) sy -
+    0.5), the pixel-centre rule of the resamplers.  The product is formed in float64 and rounded once."""
+    inv_K = np.asarray(inv_K, dtype=np.float64)
+    if inv_K.shape not in ((3, 3), (4, 4)):
+        raise ValueError("intrinsics_at: inv_K must be 3x3 or 4x4, got %s" % (inv_K.shape,))
+    (H0, W0), (h, w) = (int(v) for v in size), (int(v) for v in map_size)
+    if min(H0, W0, h, w) < 1:
+        raise ValueError("intrinsics_at: sizes must be at least 1, got %r and %r" % (size, map_size))
+    sx, sy = W0 / w, H0 / h
+    A = np.array([[sx, 0.0, 0.5 * sx - 0.5], [0.0, sy, 0.5 * sy - 0.5], [0.0, 0.0, 1.0]], dtype=np.float64)
+    return np.ascontiguousarray((inv_K[:3, :3] @ A).astype(np.float32))
+
+
 def cloud_arrays(vertices, counts, offsets):
     """What `ops.point_cloud` returned -> one structured array (`VERTEX_DTYPE`) per image.  ONE pinned read-back of the
     vertex buffer and one of the counts for the whole batch; the arrays are views into that host copy."""

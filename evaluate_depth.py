@@ -5,6 +5,8 @@
 
 `--save_clouds DIR [--cloud_count N] [--cloud_stride N] [--cloud_rays pixel|reference]` also writes the point clouds of
 the first N images, prediction and ground truth, as binary PLY files.
+`--scale_recovery ground [--camera_height 1.65] [--ground_angle 5.0]` scales every mono prediction by the camera's height
+above the pixels found to be road instead of by the LiDAR median: the scores of a model that gets no ground truth.
 """
 from baseboostdepth_amd.evaluation import evaluate
 from baseboostdepth_amd.options import MonodepthOptions

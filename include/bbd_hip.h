@@ -41,8 +41,9 @@ extern "C" {
  * 12 = bbd_post_process_disp (depth evaluation: flip post-processing of the predicted disparities);
  * 14 = bbd_pose_trajectory (KITTI odometry: full-trajectory t_rel, r_rel and aligned ATE);
  * 15 = bbd_point_cloud (coloured point clouds); 16 = bbd_map_* (voxel-fused scene map);
- * 17 = bbd_view_* (points and polylines rasterised into a z-buffered canvas). */
-#define BBD_ABI_VERSION 17
+ * 17 = bbd_view_* (points and polylines rasterised into a z-buffered canvas);
+ * 18 = bbd_ground_scale (metric scale of a prediction from the camera's height above the ground). */
+#define BBD_ABI_VERSION 18
 
 /* Source frames live in separate tensors, one per frame id (inputs[("color", f, 0)],
  * trainer.py:428).  A "slot" indexes a host array of their base pointers. */
@@ -528,6 +529,36 @@ int bbd_point_cloud(const float* pred, const float* gt, const int32_t* desc, con
                     const uint8_t* rgb, const uint8_t* lut, void* vertices, int32_t* counts, int32_t* scratch,
                     int scratch_ints, int n, int h, int w, int max_h, int max_w, int stride, double min_depth,
                     double max_depth, double clamp_lo, double clamp_hi, double scale_factor, int flags, void* stream);
+
+/* ---- Metric scale from the ground plane (csrc/bbd_ground.hip, ops.ground_scale): the factor that brings
+ * a prediction of unknown scale to metres, from the known height of the camera above the road, for n images per call.
+ *   pred    float32 [n,h,w], depth or (BBD_EVAL_PRED_IS_DISP) disparity: d = pred or 1.0f / pred; a pixel is valid
+ *           when d > 0 and finite
+ *   inv_K   float32 [n,3,3] row-major, for pixels of the h x w map itself
+ *   rows    float32 [n, BBD_EVAL_OUT], written: [0] median distance of the ground pixels' planes from the camera, in the
+ *           prediction's units, [1] their number, [2] the number of candidates, [7] camera_height / median - the slot
+ *           bbd_point_cloud reads as its ratio - all others 0.  Where the count is below max(min_count, 1), [0] and [7]
+ *           are the quiet NaN 0x7fc00000; the counts are written all the same
+ *   mask    uint8 [n,h,w] or NULL: 1 at ground pixels, 0 elsewhere, the border included
+ *   scratch float32 [bbd_ground_scale_scratch_floats(n, h, w)] = n * h * w, no initialisation needed
+ * P = bbd_syns_backproject(inv_K[i], y * w + x, h, w, pixel rays, d).  A CANDIDATE is an interior pixel (1 <= x <= w-2,
+ * 1 <= y <= h-2) whose nine pixels are all valid; maps with h < 3 or w < 3 have none.  Its normal N is the sum, in ring
+ * order, of the cross products v_k x v_(k+1) of the differences v_k = P_k - P_c to its eight neighbours (x+1,y),
+ * (x+1,y+1), (x,y+1), (x-1,y+1), (x-1,y), (x-1,y-1), (x,y-1), (x+1,y-1): +y for flat ground under a camera with x right,
+ * y down, z forward.  With len = sqrtf((N.x*N.x + N.y*N.y) + N.z*N.z), cosv = N.y / len and
+ * ht = ((N.x*P.x + N.y*P.y) + N.z*P.z) / len, the pixel is GROUND when len > 0 and finite, cosv > (float)cos_threshold,
+ * P.y > 0 and ht > 0 and finite.  The median is the element of rank (count - 1) / 2 of the ascending ht values (the
+ * lower median, exact).  All float32, one IEEE operation where written (csrc/bbd_ground_math.h, -ffp-contract=off).
+ * Two launches - a tiled pass that stages the depths of a tile and a one-pixel halo in LDS and writes one float per pixel
+ * to the scratch map, then one workgroup per image that takes the median by an 11+11+10-bit radix select on the bit
+ * patterns and writes the row - no allocation, no host synchronisation, integer counts only: identical calls give
+ * identical bytes.
+ * A NULL pred, inv_K, rows or scratch, n, h or w below 1, camera_height not above 0, cos_threshold outside (0, 1],
+ * min_count below 0 or a flag other than BBD_EVAL_PRED_IS_DISP return BBD_E_BADARG; n > 65535 or h * w > INT_MAX
+ * return BBD_E_TOOMANY.  Nothing is launched then; the size helper returns the same codes for such sizes. */
+long bbd_ground_scale_scratch_floats(int n, int h, int w);
+int bbd_ground_scale(const float* pred, const float* inv_K, float* rows, uint8_t* mask, float* scratch, int n, int h,
+                     int w, double camera_height, double cos_threshold, int min_count, int flags, void* stream);
 
 /* ---- Scene map (csrc/bbd_map.hip, pointcloud.SceneMap): the points of many frames, each placed in the
  * world by its camera-to-world pose, fused on a voxel grid into one coloured cloud.  A streaming accumulator: the state
