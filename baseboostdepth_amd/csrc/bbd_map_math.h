@@ -35,7 +35,6 @@
 
 #define BBD_MAP_EMPTY 0xffffffffffffffffull
 #define BBD_MAP_HALF 1048576 /* 2^20: voxel indices lie in (-2^20, 2^20) */
-#define BBD_MAP_MAX_T (1 << 30)
 #define BBD_MAP_CHUNK 256 /* slots per chunk of the compaction: one workgroup of four waves */
 
 /* bbd_map_point's verdicts */

@@ -32,8 +32,6 @@
 #include "bbd_math.h" /* BBD_HD */
 
 #define BBD_VIEW_EMPTY 0xffffffffffffffffull
-#define BBD_VIEW_MAX_CELLS (1L << 28)
-#define BBD_VIEW_MAX_LAYER 65535
 
 /* bbd_view_project's verdicts */
 #define BBD_VIEW_REJECTED 0

@@ -890,7 +890,7 @@ def _dwconv_groups_fwd(backend, x, x_base, x_row, y, y_base, y_row, splits, weig
 
 def _dwconv_groups_wgrad(backend, x, x_base, x_row, gy, gy_base, gy_row, splits, weights, gws, gbs, B, H, W, accumulate):
     n, c0, cn, k = _dw_group_args(splits, weights)
-    scratch = torch.empty(backend.lib.dwconv_groups_wgrad_scratch_floats(B, H, W, n, cn, k), device=x.device, dtype=torch.float32)
+    scratch = torch.empty(backend.lib.dwconv_tokens_groups_wgrad_scratch_floats(B, H, W, n, cn, k), device=x.device, dtype=torch.float32)
     backend.run("bbd_dwconv_tokens_groups_wgrad", x, _slice_ptr(x, x_base), x_row, _slice_ptr(gy, gy_base), gy_row, ptr(scratch),
                 n, c0, cn, k, _addr_array(gws), _addr_array(gbs), B, H, W, int(accumulate))
 
@@ -942,7 +942,7 @@ class _DepthwiseTokens(torch.autograd.Function):
             k = ws[0].shape[-1]
             if gx is not None:
                 backend.run("bbd_dwconv_tokens_fwd", gy, ptr(gy), C, ptr(ws[0]), ptr(None), ptr(gx), C, B, H, W, C, k, int(add_input), 1)
-            scratch = torch.empty(backend.lib.dwconv_wgrad_scratch_floats(B, H, W, C, k), device=x.device, dtype=torch.float32)
+            scratch = torch.empty(backend.lib.dwconv_tokens_wgrad_scratch_floats(B, H, W, C, k), device=x.device, dtype=torch.float32)
             backend.run("bbd_dwconv_tokens_wgrad", x, _slice_ptr(x, 0), x.stride(1), ptr(gy), C, ptr(scratch), ptr(gws[0]), ptr(gbs[0]),
                         B, H, W, C, k, acc)
         grads = []
@@ -1080,7 +1080,7 @@ def factor_attention(qkv, convv, heads, scale, backend=None):
 
 
 def factor_attention_supported(C, heads, backend=None):
-    return (backend or default_backend()).lib.factor_att_supported(C, C // heads)
+    return bool((backend or default_backend()).lib.factor_att_supported(C, C // heads))
 
 
 class _ResidualLayerNorm(torch.autograd.Function):
@@ -1182,7 +1182,7 @@ def linear_tokens(x, linear, backend=None):
 
 
 def token_glue_supported(x, backend=None):
-    return x.dim() == 3 and (backend or default_backend()).lib.token_ln_supported(x.shape[-1])
+    return x.dim() == 3 and bool((backend or default_backend()).lib.token_ln_supported(x.shape[-1]))
 
 
 def layernorm_tokens(x, norm, backend=None, passthrough=False):
@@ -1201,7 +1201,7 @@ def residual_add(x, branch, mask, backend=None):
 
 
 # ---------------------------------------------------------------------------- BatchNorm (+add) (+ReLU)
-BN_MAX_GROUPS = 32          # BBD_BN_MAX_GROUPS of include/bbd_hip.h
+BN_MAX_GROUPS = _lib.BN_MAX_GROUPS
 _bn_groups = None           # row counts of the call groups of the batched pass being run (None = one group)
 _bn_untracked = 0           # trailing groups of it that are padding (no running-statistics update)
 _bn_device = None           # (device group table, G, largest group) of `bn_call_groups_device`, or None

@@ -13,7 +13,16 @@
  *   - return value 0 = enqueued, >0 = hipError_t from the launch, <0 = BBD_E_* argument error;
  *   - tensors are fp32, contiguous, NCHW like the reference's batch dict.
  *
- * Python binding: baseboostdepth_amd/_lib.py (ctypes).  See INTEGRATION.md for the stub a
+ * Python binding: baseboostdepth_amd/_lib.py (ctypes).  It is READ FROM THIS HEADER at import (baseboostdepth_amd/_abi.py):
+ * argument and result types of every prototype, and every `#define BBD_<NAME> <integer>`, which Python sees as
+ * `_lib.<NAME>`.  A new entry point therefore needs its prototype here, its definition in a csrc .hip file, a host port under
+ * tests/host_port/ (`hp_<name>`: the same parameters minus `stream`) and the Python function that calls it - nothing else.
+ * What the reader accepts, and so what this header keeps to:
+ *   - results `int` or `long`; parameters `int`, `long`, `unsigned` or `double` by value, everything else a pointer;
+ *   - `void* stream` is the LAST parameter of every function that enqueues work; a function without it is a host-side
+ *     helper and becomes `lib.<name minus bbd_>` (one without parameters: a constant of the build, bound as its value);
+ *   - a BBD_* define is ONE integer literal: decimal, hex or a parenthesised negative - no expressions, no suffixes.
+ * Anything else makes the import raise, naming the function and parameter or the macro.  See INTEGRATION.md for the stub a
  * reference maintainer would add.
  */
 #ifndef BBD_HIP_H
@@ -616,6 +625,7 @@ int bbd_ground_scale(const float* pred, const float* inv_K, float* rows, uint8_t
 #define BBD_MAP_NO_MERGE 2
 #define BBD_MAP_COUNTERS 4
 #define BBD_MAP_SLOT_BYTES 48
+#define BBD_MAP_MAX_T 1073741824 /* 2^30: the largest table */
 long bbd_map_state_bytes(int T);
 int bbd_map_finish_scratch_ints(int T);
 int bbd_map_clear(uint64_t* keys, uint64_t* pos, uint32_t* col, int64_t* counters, int T, void* stream);
@@ -667,6 +677,8 @@ int bbd_map_finish(const uint64_t* keys, const uint64_t* pos, const uint32_t* co
  * [0, 65535], a colour outside [0, 0xffffff] or closed other than 0 or 1 return BBD_E_BADARG; H * W > 2^28 returns
  * BBD_E_TOOMANY.  Nothing is launched then. */
 #define BBD_VIEW_COUNTERS 4
+#define BBD_VIEW_MAX_CELLS 268435456 /* 2^28: the largest canvas, H * W */
+#define BBD_VIEW_MAX_LAYER 65535
 int bbd_view_clear(uint64_t* cells, int64_t* counters, int H, int W, void* stream);
 int bbd_view_points(uint64_t* cells, int64_t* counters, int H, int W, const void* vertices, const int32_t* count,
                     int n_max, const double* view, int size, void* stream);

@@ -122,13 +122,13 @@ extern "C" int hp_pose_trajectory(const float* steps, const double* gt, const do
 }
 
 // ---- stand-ins for the two launches between the frame pool and the pose buffer
-extern "C" int hp_gather_pairs(const float* pool, const int32_t* idx_a, const int32_t* idx_b, float* out, int R, int chw,
+extern "C" int hp_gather_pairs(const float* pool, const int32_t* idx_a, const int32_t* idx_b, float* out, int R, long chw,
                                double sub, double mul) {
   for (int r = 0; r < R; ++r)
     for (int half = 0; half < 2; ++half) {
       const float* src = pool + (size_t)(half ? idx_b[r] : idx_a[r]) * chw;
       float* dst = out + ((size_t)2 * r + half) * chw;
-      for (int i = 0; i < chw; ++i) dst[i] = (src[i] - (float)sub) * (float)mul;
+      for (long i = 0; i < chw; ++i) dst[i] = (src[i] - (float)sub) * (float)mul;
     }
   return 0;
 }

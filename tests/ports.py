@@ -1,6 +1,8 @@
 """Build + bind the host ports (tests/host_port/*.cpp): g++ builds of the kernels' own arithmetic (csrc/*_math.h).
 
-Test infrastructure only.  `PortBackend` plugs into the `backend=` seam of the product, so the CPU tier runs the
+Test infrastructure only.  Every `hp_<name>` with a twin `bbd_<name>` in include/bbd_hip.h is typed from that prototype
+minus the stream (`baseboostdepth_amd/_abi.py`), so a call is marshalled through a port exactly as through `HipLibrary`.
+`PortBackend` plugs into the `backend=` seam of the product, so the CPU tier runs the
 product's Python plumbing (plans, descriptor tables, scratch sizing, checks, autograd wrappers) with the exact
 arithmetic of the HIP kernels.  All ports live in ONE library, so a flow that crosses features needs no routing:
 
@@ -45,22 +47,31 @@ def build():
 
 
 class PortLibrary:
-    """`lib.<name>(ints...)` is `hp_<name>` of the port library: the size helpers of the ABI, typed by `HipLibrary`'s rule."""
+    """`lib.<name>(...)` is `hp_<name>` of the port library, for the host-side helpers of the ABI (no `stream`)."""
 
     def __init__(self, dll):
         self._dll = dll
 
     def __getattr__(self, name):
-        fn = getattr(self._dll, "hp_" + name)
-        fn.restype = ctypes.c_long if name.endswith(("_scratch_floats", "_state_bytes")) else ctypes.c_int
-        return lambda *ints: fn(*[ctypes.c_int(v) for v in ints])
+        from baseboostdepth_amd._lib import PROTOTYPES
+        proto = PROTOTYPES.get("bbd_" + name)
+        if proto is None or proto.has_stream:
+            raise AttributeError("%s is no host-side helper of include/bbd_hip.h" % name)
+        return getattr(self._dll, "hp_" + name)
 
 
 class PortBackend:
     name = "host-port"
 
     def __init__(self):
+        from baseboostdepth_amd._lib import PROTOTYPES
         self.dll = ctypes.CDLL(build())
+        # a port marshals like the product: hp_<name> takes what include/bbd_hip.h declares for bbd_<name>, minus the stream
+        for name, proto in PROTOTYPES.items():
+            fn = getattr(self.dll, "hp_" + name[len("bbd_"):], None)
+            if fn is not None:
+                fn.argtypes = [ctype for ctype, _ in proto.params[:len(proto.params) - proto.has_stream]]
+                fn.restype = proto.restype
         self.lib = PortLibrary(self.dll)
         self.calls = []
 
@@ -86,11 +97,8 @@ class PortBackend:
 
     def status(self, name, *args):
         """The return code (0 = done, < 0 = the ABI's argument errors) of the port's twin (hp_*) of the ABI function
-        `name` (bbd_*): Python floats travel as doubles, ints as C ints, everything else (ctypes pointers) as it is."""
-        fn = getattr(self.dll, name.replace("bbd_", "hp_"))
-        fn.restype = ctypes.c_int
-        return fn(*[ctypes.c_double(a) if isinstance(a, float) else ctypes.c_int(a) if isinstance(a, int) else a
-                    for a in args])
+        `name` (bbd_*), typed by the header like the library's own call."""
+        return getattr(self.dll, name.replace("bbd_", "hp_"))(*args)
 
     def run(self, name, anchor, *args):
         from baseboostdepth_amd._lib import BbdError
