@@ -732,146 +732,305 @@ __global__ __launch_bounds__(RW * RR) void maxpool3s2_bwd_kernel(const float* __
 // reflection handled by index (no padded copy), weights in LDS, deterministic weight-gradient partials.
 // ---------------------------------------------------------------------------------------------
 constexpr int DC_MAXC = 256;
-constexpr int DC_CHUNKS = 64;
+constexpr int DC_CHUNKS = 256;    // most partial rows of the weight gradient (four per lane of the final reduction)
+constexpr int DC_UC = 4;          // channels whose windows a thread of the weight gradient has in flight at once
+constexpr int DC_WAVES = NT / 64;
 
-// 3 rows x 6 columns (px0-1 .. px0+4, reflected at the image border) of one plane around a 4-pixel strip
-__device__ __forceinline__ void load_strip_window(const float* __restrict__ plane, int r0, int r1, int r2, int px0,
-                                                  int cl, int cr, float win[3][6]) {
-  const int rows[3] = {r0, r1, r2};
+// Forward and weight gradient share one layout.  W % 4 == 0 (every size the decoder has): a task is a 4-pixel strip of
+// TWO adjacent rows, so a channel costs 4 rows x (float4 + 2 halo scalars) for 8 outputs - a row is fetched twice, not
+// three times.  Other widths: a task is one pixel.  The four scales differ by 64 in pixels and by 8 in channels
+// (192 x 640 x 16 .. 24 x 80 x 128), so the CHANNELS are divided as well wherever the pixels alone would leave the
+// machine idle: between `parts` threads of a workgroup in the forward (partial sums meet in LDS, added in part order),
+// between gridDim.z workgroups in the data gradient (each writes its own planes), between gridDim.y in the weight gradient.
+struct StripTask {
+  int py0, px0;            // first row, first column
+  int rr[4];               // offsets of rows py0 - 1 .. py0 + 2 inside a plane, reflected
+  int cl, cr;              // columns left and right of the strip, reflected
+  bool has1;               // the second row py0 + 1 exists
+};
+
+__device__ __forceinline__ StripTask strip_task(int t, int H, int W) {
+  const int SW = W >> 2;
+  StripTask k;
+  const int rp = t / SW;
+  k.py0 = 2 * rp;
+  k.px0 = (t - rp * SW) << 2;
+  k.has1 = k.py0 + 1 < H;
+  k.rr[0] = reflect1(k.py0, H) * W;
+  k.rr[1] = k.py0 * W;
+  k.rr[2] = reflect1(k.py0 + 2, H) * W;
+  k.rr[3] = k.has1 ? reflect1(k.py0 + 3, H) * W : k.rr[2];
+  k.cl = reflect1(k.px0, W);
+  k.cr = reflect1(k.px0 + 5, W);
+  return k;
+}
+__device__ __forceinline__ int strip_tasks(int H, int W) { return ((H + 1) >> 1) * (W >> 2); }
+
+// 4 rows x 6 columns (px0 - 1 .. px0 + 4) of U consecutive planes
+template <int U>
+__device__ __forceinline__ void load_strip_windows(const float* __restrict__ plane, int hw, const StripTask& k,
+                                                   float win[U][4][6]) {
 #pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    const float4 m = *reinterpret_cast<const float4*>(plane + rows[r] + px0);
-    win[r][0] = plane[rows[r] + cl];
-    win[r][1] = m.x; win[r][2] = m.y; win[r][3] = m.z; win[r][4] = m.w;
-    win[r][5] = plane[rows[r] + cr];
-  }
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float* row = plane + (size_t)u * hw + k.rr[r];
+      const float4 m = *reinterpret_cast<const float4*>(row + k.px0);
+      win[u][r][0] = row[k.cl];
+      win[u][r][1] = m.x; win[u][r][2] = m.y; win[u][r][3] = m.z; win[u][r][4] = m.w;
+      win[u][r][5] = row[k.cr];
+    }
 }
 
-// One thread = 4 adjacent output pixels (W % 4 == 0: the strips and their 16-byte loads stay aligned);
-// per channel 3 x (float4 + 2 scalars) loads feed 36 multiply-adds.  Other widths: one pixel per thread.
+// the gradient that reaches the convolution's output through y = sigmoid(v): ATen's sigmoid_backward, grad * (1 - y) * y
+__device__ __forceinline__ float through_sigmoid(float g, float y) { return (g * (1.0f - y)) * y; }
+
+// y = conv(x) + bias, or its sigmoid.  Grid (groups of NT / parts tasks, N); thread (task s, part p) walks channels
+// p, p + parts, ...  The sums are kept in double (one DFMA per tap, the rate of an fp32 multiply and add kept apart),
+// and so is the sigmoid: where it is saturated, y ~ exp(v), every absolute error of v is a RELATIVE error of y and of the
+// gradient through it, and an fp32 sum of taps of size 100 is off by 1e-5.
 __global__ __launch_bounds__(NT) void dispconv_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                           const float* __restrict__ bias, float* __restrict__ y,
-                                                          int C, int H, int W) {
-  __shared__ float sw[DC_MAXC * 9];
-  for (int i = threadIdx.x; i < C * 9; i += NT) sw[i] = w[i];
+                                                          int C, int H, int W, int parts, int sigmoid) {
+  __shared__ double sw[DC_MAXC * 9];
+  __shared__ double red[8][NT];
+  for (int i = threadIdx.x; i < C * 9; i += NT) sw[i] = (double)w[i];
   __syncthreads();
-  const int hw = H * W;
+  const int hw = H * W, per = NT / parts;
+  const int part = threadIdx.x / per, s = threadIdx.x - part * per;
   const size_t n = blockIdx.y;
-  const float b = bias ? bias[0] : 0.0f;
-  if ((W & 3) == 0) {
-    const int strips = hw >> 2;
-    for (int t = blockIdx.x * NT + threadIdx.x; t < strips; t += gridDim.x * NT) {
-      const int p = t << 2;
-      const int py = p / W, px0 = p - py * W;
-      const int r0 = reflect1(py, H) * W, r1 = py * W, r2 = reflect1(py + 2, H) * W;
-      const int cl = reflect1(px0, W), cr = reflect1(px0 + 5, W);
-      float acc[4] = {b, b, b, b};
-      const float* xc = x + n * C * hw;
-      for (int c = 0; c < C; ++c, xc += hw) {
-        const float* k = sw + c * 9;
-        float win[3][6];
-        load_strip_window(xc, r0, r1, r2, px0, cl, cr, win);
+  const float* xn = x + n * C * hw;
+  const bool vec = (W & 3) == 0;
+  const int tasks = vec ? strip_tasks(H, W) : hw;
+  const int t = blockIdx.x * per + s;
+  const bool live = t < tasks;
+  double acc[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) acc[i] = 0.0;
+  StripTask k = {};
+  if (vec) {
+    k = strip_task(live ? t : tasks - 1, H, W);
+#pragma unroll 2
+    for (int c = part; c < C; c += parts) {
+      float win[1][4][6];
+      load_strip_windows<1>(xn + (size_t)c * hw, hw, k, win);
+      const double* q = sw + c * 9;
+      double d[4][6];
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int i = 0; i < 6; ++i) d[r][i] = (double)win[0][r][i];
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          acc[j] += (k[0] * win[0][j] + k[1] * win[0][j + 1] + k[2] * win[0][j + 2]) +
-                    (k[3] * win[1][j] + k[4] * win[1][j + 1] + k[5] * win[1][j + 2]) +
-                    (k[6] * win[2][j] + k[7] * win[2][j + 1] + k[8] * win[2][j + 2]);
-      }
-      *reinterpret_cast<float4*>(y + n * hw + p) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+#pragma unroll
+          for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx) acc[r * 4 + j] = fma(q[dy * 3 + dx], d[r + dy][j + dx], acc[r * 4 + j]);
     }
-    return;
-  }
-  for (int p = blockIdx.x * NT + threadIdx.x; p < hw; p += gridDim.x * NT) {
+  } else {
+    const int p = live ? t : tasks - 1;
     const int py = p / W, px = p - py * W;
-    const int r0 = reflect1(py, H) * W, r1 = py * W, r2 = reflect1(py + 2, H) * W;
-    const int c0 = reflect1(px, W), c2 = reflect1(px + 2, W);
-    float acc = b;
-    const float* xc = x + n * C * hw;
-    for (int c = 0; c < C; ++c, xc += hw) {
-      const float* k = sw + c * 9;
-      acc += (k[0] * xc[r0 + c0] + k[1] * xc[r0 + px] + k[2] * xc[r0 + c2]) +
-             (k[3] * xc[r1 + c0] + k[4] * xc[r1 + px] + k[5] * xc[r1 + c2]) +
-             (k[6] * xc[r2 + c0] + k[7] * xc[r2 + px] + k[8] * xc[r2 + c2]);
+    const int rows[3] = {reflect1(py, H) * W, py * W, reflect1(py + 2, H) * W};
+    const int cols[3] = {reflect1(px, W), px, reflect1(px + 2, W)};
+    for (int c = part; c < C; c += parts) {
+      const float* xc = xn + (size_t)c * hw;
+      const double* q = sw + c * 9;
+#pragma unroll
+      for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) acc[0] = fma(q[dy * 3 + dx], (double)xc[rows[dy] + cols[dx]], acc[0]);
     }
-    y[n * hw + p] = acc;
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) red[i][threadIdx.x] = acc[i];
+  __syncthreads();
+  if (!live) return;
+  // the parts of a task share out its outputs: each adds the partial sums of one in part order and finishes it
+  const double b = bias ? (double)bias[0] : 0.0;
+  float* yn = y + n * hw;
+  const int outs = vec ? (k.has1 ? 8 : 4) : 1;
+  for (int i = part; i < outs; i += parts) {
+    double v = 0.0;
+    for (int p = 0; p < parts; ++p) v += red[i][p * per + s];
+    v += b;
+    if (sigmoid) v = 1.0 / (1.0 + exp(-v));
+    yn[vec ? k.rr[1] + (i >> 2) * W + k.px0 + (i & 3) : t] = (float)v;
   }
 }
 
 // grad wrt x:  gx[n,c,q] = sum_d w[c][d] * G_d(q),  G_d(q) = sum over the padded positions (u,v) that
-// read q of g[n, u - dy, v - dx] (zero outside the image) - G_d is shared by all channels.
-__global__ __launch_bounds__(NT) void dispconv_bwd_data_kernel(const float* __restrict__ gy,
+// read q of g[n, u - dy, v - dx] (zero outside the image) - G_d is shared by all channels.  g = gy, or gy taken
+// through the sigmoid (y given).  Every q is read by (qy + 1, qx + 1): that term is the 3 x 3 window of the
+// zero-extended g around q.  Row 1 is also read by padded row 0, which only window row dy = 0 of output row 0 touches,
+// and row 0 is the window's own top row; likewise row H - 2 / padded row H + 1 / output row H - 1, and the columns.
+// So the border terms are sums of window entries already in registers.  Grid (NT-strip groups, N, channel parts): a
+// thread builds G of its 4-pixel strip once (one-channel reads) and writes channels z, z + gridDim.z, ... as float4.
+__global__ __launch_bounds__(NT) void dispconv_bwd_data_kernel(const float* __restrict__ gy, const float* __restrict__ y,
                                                                const float* __restrict__ w, float* __restrict__ gx,
                                                                int C, int H, int W) {
-  __shared__ float sw[DC_MAXC * 9];
-  for (int i = threadIdx.x; i < C * 9; i += NT) sw[i] = w[i];
-  __syncthreads();
   const int hw = H * W;
   const size_t n = blockIdx.y;
   const float* g = gy + n * hw;
-  for (int q = blockIdx.x * NT + threadIdx.x; q < hw; q += gridDim.x * NT) {
-    const int qy = q / W, qx = q - qy * W;
-    int us[3], vs[3], nu = 0, nv = 0;          // padded coordinates (0..H+1, 0..W+1) mapping onto (qy, qx)
-    us[nu++] = qy + 1;
-    if (qy == 1) us[nu++] = 0;
-    if (qy == H - 2) us[nu++] = H + 1;
-    vs[nv++] = qx + 1;
-    if (qx == 1) vs[nv++] = 0;
-    if (qx == W - 2) vs[nv++] = W + 1;
-    float G[9];
+  const float* yn = y ? y + n * hw : nullptr;
+  auto at = [&](int i) { return yn ? through_sigmoid(g[i], yn[i]) : g[i]; };
+  const int t = blockIdx.x * NT + threadIdx.x;
+  if ((W & 3) == 0) {
+    if (t >= (hw >> 2)) return;
+    const int q = t << 2;
+    const int qy = q / W, qx0 = q - qy * W;
+    float win[3][6];
 #pragma unroll
-    for (int d = 0; d < 9; ++d) G[d] = 0.0f;
-    for (int a = 0; a < nu; ++a)
-      for (int b = 0; b < nv; ++b) {
+    for (int r = 0; r < 3; ++r) {
+      const int row = qy - 1 + r;
 #pragma unroll
-        for (int dy = 0; dy < 3; ++dy) {
-          const int py = us[a] - dy;           // output row whose window row dy sits on padded row us[a]
-          if (py < 0 || py >= H) continue;
+      for (int i = 0; i < 6; ++i) win[r][i] = 0.0f;
+      if (row < 0 || row >= H) continue;
+      const int o = row * W + qx0;
+      float4 m = *reinterpret_cast<const float4*>(g + o);
+      if (yn) {
+        const float4 s = *reinterpret_cast<const float4*>(yn + o);
+        m.x = through_sigmoid(m.x, s.x); m.y = through_sigmoid(m.y, s.y);
+        m.z = through_sigmoid(m.z, s.z); m.w = through_sigmoid(m.w, s.w);
+      }
+      win[r][1] = m.x; win[r][2] = m.y; win[r][3] = m.z; win[r][4] = m.w;
+      if (qx0 > 0) win[r][0] = at(o - 1);
+      if (qx0 + 4 < W) win[r][5] = at(o + 4);
+    }
+    float G[4][9];
 #pragma unroll
-          for (int dx = 0; dx < 3; ++dx) {
-            const int px = vs[b] - dx;
-            if (px < 0 || px >= W) continue;
-            G[dy * 3 + dx] += g[py * W + px];
-          }
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) G[j][dy * 3 + dx] = win[2 - dy][j + 2 - dx];
+    const bool top = qy == 1, bottom = qy == H - 2;           // both at H == 3
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int dx = 0; dx < 3; ++dx) {
+        if (top) G[j][dx] += win[0][j + 2 - dx];
+        if (bottom) G[j][6 + dx] += win[2][j + 2 - dx];
+      }
+    if (qx0 == 0) {                                           // qx = 1 is also read by padded column 0
+#pragma unroll
+      for (int dy = 0; dy < 3; ++dy) G[1][dy * 3] += win[2 - dy][1];
+      if (top) G[1][0] += win[0][1];
+      if (bottom) G[1][6] += win[2][1];
+    }
+    if (qx0 + 4 == W) {                                       // qx = W - 2 by padded column W + 1
+#pragma unroll
+      for (int dy = 0; dy < 3; ++dy) G[2][dy * 3 + 2] += win[2 - dy][4];
+      if (top) G[2][2] += win[0][4];
+      if (bottom) G[2][8] += win[2][4];
+    }
+    for (int c = blockIdx.z; c < C; c += gridDim.z) {
+      const float* k = w + c * 9;
+      float v[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        v[j] = ((k[0] * G[j][0] + k[1] * G[j][1] + k[2] * G[j][2]) + (k[3] * G[j][3] + k[4] * G[j][4] + k[5] * G[j][5])) +
+               (k[6] * G[j][6] + k[7] * G[j][7] + k[8] * G[j][8]);
+      *reinterpret_cast<float4*>(gx + (n * C + c) * hw + q) = make_float4(v[0], v[1], v[2], v[3]);
+    }
+    return;
+  }
+  if (t >= hw) return;
+  const int qy = t / W, qx = t - qy * W;
+  int us[3], vs[3], nu = 0, nv = 0;            // padded coordinates (0..H+1, 0..W+1) mapping onto (qy, qx)
+  us[nu++] = qy + 1;
+  if (qy == 1) us[nu++] = 0;
+  if (qy == H - 2) us[nu++] = H + 1;
+  vs[nv++] = qx + 1;
+  if (qx == 1) vs[nv++] = 0;
+  if (qx == W - 2) vs[nv++] = W + 1;
+  float G[9];
+#pragma unroll
+  for (int d = 0; d < 9; ++d) G[d] = 0.0f;
+  for (int a = 0; a < nu; ++a)
+    for (int b = 0; b < nv; ++b) {
+#pragma unroll
+      for (int dy = 0; dy < 3; ++dy) {
+        const int py = us[a] - dy;             // output row whose window row dy sits on padded row us[a]
+        if (py < 0 || py >= H) continue;
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+          const int px = vs[b] - dx;
+          if (px < 0 || px >= W) continue;
+          G[dy * 3 + dx] += at(py * W + px);
         }
       }
-    float* o = gx + n * C * hw + q;
-    for (int c = 0; c < C; ++c, o += hw) {
-      const float* k = sw + c * 9;
-      *o = ((k[0] * G[0] + k[1] * G[1] + k[2] * G[2]) + (k[3] * G[3] + k[4] * G[4] + k[5] * G[5])) +
-           (k[6] * G[6] + k[7] * G[7] + k[8] * G[8]);
     }
+  for (int c = blockIdx.z; c < C; c += gridDim.z) {
+    const float* k = w + c * 9;
+    gx[(n * C + c) * hw + t] = ((k[0] * G[0] + k[1] * G[1] + k[2] * G[2]) + (k[3] * G[3] + k[4] * G[4] + k[5] * G[5])) +
+                               (k[6] * G[6] + k[7] * G[7] + k[8] * G[8]);
   }
 }
 
-// grad wrt w (and bias): block (chunk, c) accumulates its slice of the N*H*W pixels; fp64 partials.
+// grad wrt w (and bias): block (chunk, group of DC_UC channels) accumulates its share of the N * tasks tasks in fp32
+// per thread, fp64 from there on; g is read once for the group's channels and their DC_UC windows (48 loads) are in
+// flight together.  gridDim.x = as many chunks as there are workgroups' worth of tasks, DC_CHUNKS at the most.  A last,
+// ragged group loads channel C - 1 in its spare slots and drops what they add up.  Every group forms the bias column;
+// the final kernel reads channel 0's.
 __global__ __launch_bounds__(NT) void dispconv_bwd_weight_kernel(const float* __restrict__ x,
                                                                  const float* __restrict__ gy,
+                                                                 const float* __restrict__ y,
                                                                  double* __restrict__ part, int N, int C, int H,
                                                                  int W) {
-  __shared__ double sh[4];
-  const int c = blockIdx.y, hw = H * W;
-  float acc[10];
+  constexpr int TOTALS = DC_UC * 9 + 1;
+  __shared__ double sh[DC_WAVES][TOTALS];
+  const int hw = H * W, c0 = blockIdx.y * DC_UC;
+  float acc[TOTALS];
 #pragma unroll
-  for (int d = 0; d < 10; ++d) acc[d] = 0.0f;
+  for (int i = 0; i < TOTALS; ++i) acc[i] = 0.0f;
   if ((W & 3) == 0) {
-    const long long strips = ((long long)N * hw) >> 2;
-    for (long long t = (long long)blockIdx.x * NT + threadIdx.x; t < strips; t += (long long)gridDim.x * NT) {
-      const long long i = t << 2;
-      const int n = (int)(i / hw), p = (int)(i - (long long)n * hw);
-      const int py = p / W, px0 = p - py * W;
-      const float4 g4 = *reinterpret_cast<const float4*>(gy + i);
-      const float g[4] = {g4.x, g4.y, g4.z, g4.w};
-      const float* xc = x + ((size_t)n * C + c) * hw;
-      float win[3][6];
-      load_strip_window(xc, reflect1(py, H) * W, py * W, reflect1(py + 2, H) * W, px0, reflect1(px0, W),
-                        reflect1(px0 + 5, W), win);
+    const int tasks = strip_tasks(H, W);
+    const long long total = (long long)N * tasks;
+    for (long long t = (long long)blockIdx.x * NT + threadIdx.x; t < total; t += (long long)gridDim.x * NT) {
+      const int n = (int)(t / tasks);
+      const StripTask k = strip_task((int)(t - (long long)n * tasks), H, W);
+      float g[2][4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
+      for (int r = 0; r < 2; ++r) {
+        if (r == 1 && !k.has1) {
+          g[1][0] = g[1][1] = g[1][2] = g[1][3] = 0.0f;
+          continue;
+        }
+        const size_t o = (size_t)n * hw + k.rr[1] + r * W + k.px0;
+        float4 m = *reinterpret_cast<const float4*>(gy + o);
+        if (y) {
+          const float4 s = *reinterpret_cast<const float4*>(y + o);
+          m.x = through_sigmoid(m.x, s.x); m.y = through_sigmoid(m.y, s.y);
+          m.z = through_sigmoid(m.z, s.z); m.w = through_sigmoid(m.w, s.w);
+        }
+        g[r][0] = m.x; g[r][1] = m.y; g[r][2] = m.z; g[r][3] = m.w;
+      }
+      float win[DC_UC][4][6];
 #pragma unroll
-        for (int r = 0; r < 3; ++r)
+      for (int u = 0; u < DC_UC; ++u) {
+        float one[1][4][6];
+        load_strip_windows<1>(x + ((size_t)n * C + min(c0 + u, C - 1)) * hw, hw, k, one);
 #pragma unroll
-          for (int d = 0; d < 3; ++d) acc[r * 3 + d] += g[j] * win[r][j + d];
-        acc[9] += g[j];
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int i = 0; i < 6; ++i) win[u][r][i] = one[0][r][i];
+      }
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        if (r == 1 && !k.has1) continue;                      // no 0 * inf from the row below the image
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+#pragma unroll
+          for (int u = 0; u < DC_UC; ++u)
+#pragma unroll
+            for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+              for (int dx = 0; dx < 3; ++dx)
+                acc[u * 9 + dy * 3 + dx] = fmaf(g[r][j], win[u][r + dy][j + dx], acc[u * 9 + dy * 3 + dx]);
+          acc[TOTALS - 1] += g[r][j];
+        }
       }
     }
   } else {
@@ -879,30 +1038,50 @@ __global__ __launch_bounds__(NT) void dispconv_bwd_weight_kernel(const float* __
     for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < total; i += (long long)gridDim.x * NT) {
       const int n = (int)(i / hw), p = (int)(i - (long long)n * hw);
       const int py = p / W, px = p - py * W;
-      const float g = gy[i];
-      const float* xc = x + ((size_t)n * C + c) * hw;
-      const int r0 = reflect1(py, H) * W, r1 = py * W, r2 = reflect1(py + 2, H) * W;
-      const int c0 = reflect1(px, W), c2 = reflect1(px + 2, W);
-      acc[0] += g * xc[r0 + c0]; acc[1] += g * xc[r0 + px]; acc[2] += g * xc[r0 + c2];
-      acc[3] += g * xc[r1 + c0]; acc[4] += g * xc[r1 + px]; acc[5] += g * xc[r1 + c2];
-      acc[6] += g * xc[r2 + c0]; acc[7] += g * xc[r2 + px]; acc[8] += g * xc[r2 + c2];
-      acc[9] += g;
+      const float gi = y ? through_sigmoid(gy[i], y[i]) : gy[i];
+      const int rows[3] = {reflect1(py, H) * W, py * W, reflect1(py + 2, H) * W};
+      const int cols[3] = {reflect1(px, W), px, reflect1(px + 2, W)};
+#pragma unroll
+      for (int u = 0; u < DC_UC; ++u) {
+        const float* xc = x + ((size_t)n * C + min(c0 + u, C - 1)) * hw;
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+          for (int dx = 0; dx < 3; ++dx) acc[u * 9 + dy * 3 + dx] += gi * xc[rows[dy] + cols[dx]];
+      }
+      acc[TOTALS - 1] += gi;
     }
   }
+  // wave sums of all totals side by side - no barrier between them - then ONE exchange through LDS, waves in index order
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-  for (int d = 0; d < 10; ++d) {
-    const double t = block_sum((double)acc[d], sh);
-    if (threadIdx.x == 0) part[((size_t)blockIdx.x * C + c) * 10 + d] = t;
+  for (int i = 0; i < TOTALS; ++i) {
+    double v = (double)acc[i];
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if (lane == 0) sh[wave][i] = v;
+  }
+  __syncthreads();
+  static_assert(DC_WAVES == 4, "the sum below names the four waves");
+  if (threadIdx.x >= TOTALS) return;
+  const int i = threadIdx.x;
+  const double total = (sh[0][i] + sh[1][i]) + (sh[2][i] + sh[3][i]);
+  double* row = part + (size_t)blockIdx.x * C * 10;
+  if (i < TOTALS - 1) {
+    const int u = i / 9;
+    if (c0 + u < C) row[(c0 + u) * 10 + (i - u * 9)] = total;
+  } else {
+    for (int u = 0; u < DC_UC && c0 + u < C; ++u) row[(c0 + u) * 10 + 9] = total;
   }
 }
 
-// one wave per output: lanes = chunks (DC_CHUNKS == 64), fixed-order butterfly
+// one wave per output: lane l adds chunks l, l + 64, ... in that order, then a fixed-order butterfly
 __global__ __launch_bounds__(64) void dispconv_bwd_weight_final_kernel(const double* __restrict__ part,
                                                                       float* __restrict__ gw, float* __restrict__ gb,
-                                                                      int C) {
+                                                                      int C, int chunks) {
   const int i = blockIdx.x;                    // 0 .. C*9 (the last one is the bias)
   const int c = i < C * 9 ? i / 9 : 0, d = i < C * 9 ? i - c * 9 : 9;
-  double v = part[((size_t)threadIdx.x * C + c) * 10 + d];
+  double v = 0.0;
+  for (int k = threadIdx.x; k < chunks; k += 64) v += part[((size_t)k * C + c) * 10 + d];
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
   if (threadIdx.x == 0) {
     if (i < C * 9) gw[i] = (float)v;
@@ -1135,33 +1314,70 @@ int bbd_maxpool3s2_bwd(const float* grad_out, const uint8_t* code, float* grad_i
 
 int bbd_dispconv_scratch_doubles(int C) { return DC_CHUNKS * C * 10; }
 
+namespace {
+constexpr long DC_FILL = 65536;      // threads' worth of tasks from which on the pixels alone fill the machine
+constexpr long DC_RESIDENT = 1024;  // workgroups of the weight gradient that the machine holds at once
+
+int launch_dispconv_fwd(const float* x, const float* weight, const float* bias, float* y, int N, int C, int H, int W,
+                        int sigmoid, void* stream) {
+  if (!x || !weight || !y || N <= 0 || N > 65535 || C <= 0 || C > DC_MAXC || H < 2 || W < 2) return BBD_E_BADARG;
+  const int tasks = (W & 3) == 0 ? ((H + 1) / 2) * (W / 4) : H * W;
+  const int parts = (long)N * tasks * 4 >= DC_FILL ? 4 : 16;
+  const int per = NT / parts;
+  hipLaunchKernelGGL(dispconv_fwd_kernel, dim3((unsigned)((tasks + per - 1) / per), (unsigned)N), dim3(NT), 0,
+                     static_cast<hipStream_t>(stream), x, weight, bias, y, C, H, W, parts, sigmoid);
+  return status();
+}
+int launch_dispconv_bwd(const float* x, const float* weight, const float* y, const float* grad_y, float* grad_x,
+                        float* grad_weight, float* grad_bias, double* scratch, int N, int C, int H, int W, void* stream) {
+  if (!x || !weight || !grad_y || !scratch || N <= 0 || N > 65535 || C <= 0 || C > DC_MAXC || H < 2 || W < 2)
+    return BBD_E_BADARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool vec = (W & 3) == 0;
+  if (grad_x) {
+    const int work = vec ? H * W / 4 : H * W;
+    long z = (DC_FILL + (long)N * work - 1) / ((long)N * work);
+    z = z < 1 ? 1 : z > C ? C : z;
+    hipLaunchKernelGGL(dispconv_bwd_data_kernel, dim3((unsigned)((work + NT - 1) / NT), (unsigned)N, (unsigned)z), dim3(NT), 0,
+                       st, grad_y, y, weight, grad_x, C, H, W);
+  }
+  if (grad_weight) {
+    // one workgroup's worth of tasks per chunk, but no more workgroups than are resident at once (4 per CU at this
+    // kernel's 127 registers, 256 CUs): beyond that a workgroup only waits for a slot and adds an epilogue
+    const long total = (long)N * (vec ? ((H + 1) / 2) * (W / 4) : H * W);
+    const int groups = (C + DC_UC - 1) / DC_UC;
+    long chunks = (total + NT - 1) / NT;
+    const long resident = DC_RESIDENT / groups > 1 ? DC_RESIDENT / groups : 1;
+    chunks = chunks > resident ? resident : chunks;
+    chunks = chunks > DC_CHUNKS ? DC_CHUNKS : chunks;
+    hipLaunchKernelGGL(dispconv_bwd_weight_kernel, dim3((unsigned)chunks, (unsigned)groups), dim3(NT), 0,
+                       st, x, grad_y, y, scratch, N, C, H, W);
+    hipLaunchKernelGGL(dispconv_bwd_weight_final_kernel, dim3((unsigned)(C * 9 + 1)), dim3(64), 0, st, scratch,
+                       grad_weight, grad_bias, C, (int)chunks);
+  }
+  return status();
+}
+}  // namespace
+
 int bbd_dispconv_fwd(const float* x, const float* weight, const float* bias, float* y, int N, int C, int H, int W,
                      void* stream) {
-  if (!x || !weight || !y || N <= 0 || C <= 0 || C > DC_MAXC || H < 2 || W < 2) return BBD_E_BADARG;
-  const int hw = H * W;
-  const int work = (W & 3) == 0 ? hw / 4 : hw;
-  const unsigned gx = (unsigned)((work + NT - 1) / NT);
-  hipLaunchKernelGGL(dispconv_fwd_kernel, dim3(gx, (unsigned)N), dim3(NT), 0, static_cast<hipStream_t>(stream), x,
-                     weight, bias, y, C, H, W);
-  return status();
+  return launch_dispconv_fwd(x, weight, bias, y, N, C, H, W, 0, stream);
 }
 
 int bbd_dispconv_bwd(const float* x, const float* weight, const float* grad_y, float* grad_x, float* grad_weight,
                      float* grad_bias, double* scratch, int N, int C, int H, int W, void* stream) {
-  if (!x || !weight || !grad_y || !scratch || N <= 0 || C <= 0 || C > DC_MAXC || H < 2 || W < 2) return BBD_E_BADARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int hw = H * W;
-  if (grad_x)
-    hipLaunchKernelGGL(dispconv_bwd_data_kernel, dim3((unsigned)((hw + NT - 1) / NT), (unsigned)N), dim3(NT), 0, st,
-                       grad_y, weight, grad_x, C, H, W);
-  if (grad_weight) {
-    hipLaunchKernelGGL(dispconv_bwd_weight_kernel, dim3((unsigned)DC_CHUNKS, (unsigned)C), dim3(NT), 0, st, x, grad_y,
-                       scratch, N, C, H, W);
-    static_assert(DC_CHUNKS == 64, "the final reduction maps chunks onto the 64 lanes of a wave");
-    hipLaunchKernelGGL(dispconv_bwd_weight_final_kernel, dim3((unsigned)(C * 9 + 1)), dim3(64), 0, st, scratch,
-                       grad_weight, grad_bias, C);
-  }
-  return status();
+  return launch_dispconv_bwd(x, weight, nullptr, grad_y, grad_x, grad_weight, grad_bias, scratch, N, C, H, W, stream);
+}
+
+int bbd_disp_head_fwd(const float* x, const float* weight, const float* bias, float* disp, int N, int C, int H, int W,
+                      void* stream) {
+  return launch_dispconv_fwd(x, weight, bias, disp, N, C, H, W, 1, stream);
+}
+
+int bbd_disp_head_bwd(const float* x, const float* weight, const float* disp, const float* grad_disp, float* grad_x,
+                      float* grad_weight, float* grad_bias, double* scratch, int N, int C, int H, int W, void* stream) {
+  if (!disp) return BBD_E_BADARG;
+  return launch_dispconv_bwd(x, weight, disp, grad_disp, grad_x, grad_weight, grad_bias, scratch, N, C, H, W, stream);
 }
 
 }  // extern "C"

@@ -57,7 +57,12 @@ class DepthDecoder(nn.Module):
                     x = torch.cat([x, skip], 1)
                 x = self._stage("upconv", level, 1)(x)
             if level in self.scales:
-                self.outputs[("disp", level)] = torch.sigmoid(self._stage("dispconv", level)(x))
+                head = self._stage("dispconv", level)
+                if head._fused(x):
+                    # convolution to one channel and its sigmoid in ONE HIP pass each way
+                    self.outputs[("disp", level)] = ops.disp_head(x, head.conv.weight, head.conv.bias)
+                else:
+                    self.outputs[("disp", level)] = torch.sigmoid(head(x))
         return self.outputs
 
 

@@ -1495,6 +1495,41 @@ def dispconv(x, weight, bias, backend=None):
     return _DispConv.apply(x, weight, bias, backend or default_backend())
 
 
+class _DispHead(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, backend):
+        x = x.contiguous()
+        N, C, H, W = x.shape
+        w = weight.contiguous()
+        backend._check(x, w, bias)
+        disp = torch.empty(N, 1, H, W, device=x.device, dtype=torch.float32)
+        backend.run("bbd_disp_head_fwd", x, ptr(x), ptr(w), ptr(bias), ptr(disp), N, C, H, W)
+        ctx.save_for_backward(x, w, disp)
+        ctx.meta = (bias is not None, backend)
+        return disp
+
+    @staticmethod
+    def backward(ctx, grad_disp):
+        x, w, disp = ctx.saved_tensors
+        has_bias, backend = ctx.meta
+        N, C, H, W = x.shape
+        grad_disp = grad_disp.contiguous()
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2])
+        grad_x = torch.empty_like(x) if need_x else None
+        grad_w = torch.empty_like(w) if need_w else None
+        grad_b = torch.empty(1, device=x.device, dtype=torch.float32) if (need_w and has_bias) else None
+        scratch = torch.empty(backend.lib.dispconv_scratch_doubles(C), device=x.device, dtype=torch.float64)
+        backend.run("bbd_disp_head_bwd", x, ptr(x), ptr(w), ptr(disp), ptr(grad_disp), ptr(grad_x), ptr(grad_w),
+                    ptr(grad_b), ptr(scratch), N, C, H, W)
+        return grad_x, grad_w, grad_b, None
+
+
+def disp_head(x, weight, bias, backend=None):
+    """sigmoid(dispconv(x, weight, bias)): the decoder's disparity output in one launch, and a backward that takes the
+    gradient through the sigmoid inside the two gradient kernels."""
+    return _DispHead.apply(x, weight, bias, backend or default_backend())
+
+
 # ---------------------------------------------------------------------------- colour-mapped disparity
 _MAGMA = {}
 

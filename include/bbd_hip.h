@@ -51,8 +51,9 @@ extern "C" {
  * 14 = bbd_pose_trajectory (KITTI odometry: full-trajectory t_rel, r_rel and aligned ATE);
  * 15 = bbd_point_cloud (coloured point clouds); 16 = bbd_map_* (voxel-fused scene map);
  * 17 = bbd_view_* (points and polylines rasterised into a z-buffered canvas);
- * 18 = bbd_ground_scale (metric scale of a prediction from the camera's height above the ground). */
-#define BBD_ABI_VERSION 18
+ * 18 = bbd_ground_scale (metric scale of a prediction from the camera's height above the ground);
+ * 19 = bbd_disp_head_fwd / _bwd (the disparity head with its sigmoid inside). */
+#define BBD_ABI_VERSION 19
 
 /* Source frames live in separate tensors, one per frame id (inputs[("color", f, 0)],
  * trainer.py:428).  A "slot" indexes a host array of their base pointers. */
@@ -861,6 +862,15 @@ int bbd_dispconv_fwd(const float* x, const float* weight, const float* bias, flo
                      void* stream);
 int bbd_dispconv_bwd(const float* x, const float* weight, const float* grad_y, float* grad_x, float* grad_weight,
                      float* grad_bias, double* scratch, int N, int C, int H, int W, void* stream);
+
+/* The same layer with the decoder's sigmoid inside (networks/depth_decoder.py:58): disp = sigmoid(dispconv(x)) in one
+ * launch, nothing but disp [N,1,H,W] written.  The backward takes grad_disp [N,1,H,W] and forms
+ * grad_disp * (1 - disp) * disp (ATen's sigmoid_backward) on the fly inside both gradient kernels; arguments otherwise
+ * as bbd_dispconv_bwd, scratch of the same size. */
+int bbd_disp_head_fwd(const float* x, const float* weight, const float* bias, float* disp, int N, int C, int H, int W,
+                      void* stream);
+int bbd_disp_head_bwd(const float* x, const float* weight, const float* disp, const float* grad_disp, float* grad_x,
+                      float* grad_weight, float* grad_bias, double* scratch, int N, int C, int H, int W, void* stream);
 
 /* Input of the batched pose pass in the pooled form of the step: out [R, 2, chw] row r = the image pair
  * (pool[idx_a[r]], pool[idx_b[r]]) of the frame pool [F, chw] (chw = 3*H*W floats, multiple of 4), every texel (v - sub) * mul.
