@@ -39,6 +39,7 @@ SRCS = _here("""
     bbd_ground.hip
     bbd_map.hip
     bbd_view.hip
+    bbd_consist.hip
 """)
 OUT = os.path.join(HERE, "libbbd_hip.so")
 # every header of this directory: one that is forgotten here would leave a stale library behind an edit

@@ -857,6 +857,16 @@ def evaluate_pose(opt, dataloader=None, gt_poses=None, models=None, batch_window
     `opt.save_map` is given, with a disc at the start and a scale bar.  It is drawn on the device from what is already
     there and read back once.  One more line is printed and the dict gains `plot_stats` (view, m_per_px, scale_bar and
     the voxels offered, drawn, clipped, rejected) and `plot_path`.
+
+    `opt.consistency` (needs `opt.trajectory`) scores whether the depth network and the pose network agree, without
+    ground truth (`_consistency`): the disparities of every `opt.map_every`-th frame are predicted once, each
+    frame's pixels are moved into its `opt.consistency_views` neighbours on either side with the aligned trajectory and
+    compared with the depth predicted there, err = |z - d_b| / (z + d_b).  One more line is printed after the trajectory
+    line and the dict gains `consistency` (views, threshold, min_views, frames, mean_err, agree_share, kept_share and the
+    five totals valid, visible, consistent, err_sum, kept), from one read-back of the counters.  `opt.map_consistent`
+    (needs `opt.save_map`) implies it and fuses the map from the filtered disparities - pixels that agree in fewer than
+    `opt.consistency_min_views` neighbours are offered as disparity 0, which the map rejects like any other disparity
+    without a finite depth: `map_stats["kept"]` falls by their number, no other statistic moves.
     `backend` / `device` are the seam of the test tier (default: the HIP backend on `cuda:<opt.cuda>`)."""
     import os
     from . import datasets, networks, tuning
@@ -872,7 +882,14 @@ def evaluate_pose(opt, dataloader=None, gt_poses=None, models=None, batch_window
     save_map = getattr(opt, "save_map", None)
     if save_map and not trajectory:
         raise ValueError("evaluate_pose: --save_map needs --trajectory")
-    map_opt = _map_options(opt) if save_map else None
+    map_consistent = bool(getattr(opt, "map_consistent", False))
+    if map_consistent and not save_map:
+        raise ValueError("evaluate_pose: --map_consistent needs --save_map")
+    consistency = bool(getattr(opt, "consistency", False)) or map_consistent
+    if consistency and not trajectory:
+        raise ValueError("evaluate_pose: --consistency needs --trajectory")
+    map_opt = _map_options(opt) if save_map or consistency else None
+    consist_opt = _consistency_options(opt) if consistency else None
     save_plot = getattr(opt, "save_plot", None)
     if save_plot and not trajectory:
         raise ValueError("evaluate_pose: --save_plot needs --trajectory")
@@ -901,7 +918,7 @@ def evaluate_pose(opt, dataloader=None, gt_poses=None, models=None, batch_window
         encoder, decoder = models[:2]
     encoder.to(device).eval()
     decoder.to(device).eval()
-    predictor = _map_predictor(opt, models, height, width, device, backend) if save_map else None
+    predictor = _map_predictor(opt, models, height, width, device, backend) if save_map or consistency else None
     if dataloader is None:
         pool_set = datasets.KITTIOdomDataset(frames, 0, height, width, kt_path=opt.kt_path, is_train=False, kt=True,
                                              naive_mix=True, odom_path=odom_root)
@@ -961,11 +978,19 @@ def evaluate_pose(opt, dataloader=None, gt_poses=None, models=None, batch_window
                       out["traj_scale"]))
         if save_trajectory:
             np.savetxt(save_trajectory, both[0].reshape(frames_scored, 16)[:, :12], fmt="%.6e")
+        if (save_map or consistency) and F != frames_scored:
+            raise ValueError("evaluate_pose: %s needs the frames of one side of one sequence: the pool holds %d frames, "
+                             "the trajectory %d" % ("--save_map" if save_map else "--consistency", F, frames_scored))
+        filtered = None
+        if consistency:
+            out["consistency"], filtered = _consistency(predictor, pool, tr, map_opt["every"], consist_opt, map_consistent,
+                                                        backend)
+            print("   Depth-pose consistency (views {views:d}, threshold {threshold:g}, {frames:d} frames): mean err "
+                  "{mean_err:0.4f}, {:0.2f} % of visible samples agree, {:0.2f} % of valid pixels kept\n"
+                  .format(100.0 * out["consistency"]["agree_share"], 100.0 * out["consistency"]["kept_share"],
+                          **out["consistency"]))
         if save_map:
-            if F != frames_scored:
-                raise ValueError("evaluate_pose: --save_map needs the frames of one side of one sequence: the pool holds "
-                                 "%d frames, the trajectory %d" % (F, frames_scored))
-            out["map_stats"], scene = _scene_map(predictor, pool, tr, map_opt, save_map, backend)
+            out["map_stats"], scene = _scene_map(predictor, pool, tr, map_opt, save_map, backend, disps=filtered)
             out["map_path"] = save_map
             print("   Scene map: {frames:d} frames, {candidates:d} candidates, {kept:d} kept, {voxels:d} voxels -> {}\n"
                   .format(save_map, **out["map_stats"]))
@@ -1011,10 +1036,11 @@ def _map_predictor(opt, models, height, width, device, backend):
     return predictor
 
 
-def _scene_map(predictor, pool, tr, m, path, backend=None):
+def _scene_map(predictor, pool, tr, m, path, backend=None, disps=None):
     """The scene map of a sequence: every `every`-th frame of `pool` [F,3,H,W] through the depth network in batches, each
     batch straight into `SceneMap.add` with its rows of `tr.aligned` and the scale `tr.summary[6:7]` (1 under se3 / none)
-    - nothing is read back before `finish`.  Writes `path`; returns the statistics and the map."""
+    - nothing is read back before `finish`.  `disps` ([R,H,W], one row per selected frame: `_consistency`'s filtered
+    disparities) takes the place of the network pass.  Writes `path`; returns the statistics and the map."""
     from . import pointcloud
     F, _, H, W = pool.shape
     scene = pointcloud.SceneMap(m["voxel"], m["capacity"], pool.device, backend)
@@ -1025,13 +1051,85 @@ def _scene_map(predictor, pool, tr, m, path, backend=None):
         for lo in range(0, len(rows), predictor.batch_size):
             sel = slice(rows[lo], rows[min(lo + predictor.batch_size, len(rows)) - 1] + 1, m["every"])
             rgb = pool[sel].contiguous()
-            disp = min_disp + (max_disp - min_disp) * predictor.disparity(rgb)
+            if disps is None:
+                disp = min_disp + (max_disp - min_disp) * predictor.disparity(rgb)
+            else:
+                disp = disps[lo:lo + predictor.batch_size]
             scene.add(disp, rgb, tr.aligned[sel].contiguous(), inv_K, scale=tr.summary[6:7], stride=m["stride"],
                       min_depth=m["min_depth"], max_depth=m["max_depth"])
         vertices, _, stats = scene.finish(m["min_points"])
     pointcloud.write_ply(path, vertices)
     stats["frames"] = len(rows)
     return stats, scene
+
+
+CONSISTENCY_CHUNK = 64           # frames per `ops.depth_consistency` call of `_consistency`, neighbours not counted
+
+
+def _consistency_options(opt):
+    """The --consistency_* options of `opt` with their defaults, checked."""
+    from ._lib import CONSIST_MAX_VIEWS
+    c = {"views": int(getattr(opt, "consistency_views", 1)), "threshold": float(getattr(opt, "consistency_threshold", 0.05)),
+         "min_views": int(getattr(opt, "consistency_min_views", 1))}
+    if not 1 <= 2 * c["views"] <= CONSIST_MAX_VIEWS:
+        raise ValueError("evaluate_pose: --consistency_views must lie in [1, %d], got %d" % (CONSIST_MAX_VIEWS // 2, c["views"]))
+    if not c["threshold"] >= 0.0:
+        raise ValueError("evaluate_pose: --consistency_threshold must not be negative, got %r" % c["threshold"])
+    if c["min_views"] < 0:
+        raise ValueError("evaluate_pose: --consistency_min_views must not be negative, got %d" % c["min_views"])
+    return c
+
+
+def consistency_offsets(views):
+    """The neighbours of --consistency_views k: -1, 1, -2, 2, ... -k, k."""
+    return tuple(o for k in range(1, int(views) + 1) for o in (-k, k))
+
+
+def _consistency(predictor, pool, tr, every, c, want_filtered, backend=None):
+    """Depth-pose consistency of a sequence: every `every`-th frame of `pool` [F,3,H,W] through the depth network once,
+    into one [R,H,W] buffer of scaled disparities; then `ops.depth_consistency` over it in chunks of CONSISTENCY_CHUNK frames, each
+    with the `views` neighbours it needs on either side (they ride along without sources of their own, and what the call
+    writes for them is dropped), with the rows of `tr.aligned` and the scale `tr.summary[6:7]`.  The per-frame counters
+    are summed on the device and read back once.  Returns (the `consistency` dict, the filtered disparities [R,H,W] on
+    the device or None)."""
+    from . import pointcloud
+    F, _, H, W = pool.shape
+    dev = pool.device
+    K = upload(np.ascontiguousarray(pointcloud.camera_matrix(H, W)[:3, :3]), dev)
+    inv_K = upload(pointcloud.intrinsics(H, W), dev)
+    min_disp, max_disp = 1.0 / predictor.max_depth, 1.0 / predictor.min_depth
+    rows = list(range(0, F, every))
+    R, k = len(rows), c["views"]
+    chunk = int(CONSISTENCY_CHUNK)
+    disps = torch.empty(R, H, W, dtype=torch.float32, device=dev)
+    filtered = torch.empty(R, H, W, dtype=torch.float32, device=dev) if want_filtered else None
+    poses = tr.aligned[::every].contiguous()
+    table = pointcloud.neighbour_sources(R, consistency_offsets(k))
+    totals = torch.zeros(5, dtype=torch.int64, device=dev)
+    with torch.no_grad():
+        for lo in range(0, R, predictor.batch_size):
+            sel = slice(rows[lo], rows[min(lo + predictor.batch_size, R) - 1] + 1, every)
+            disp = min_disp + (max_disp - min_disp) * predictor.disparity(pool[sel].contiguous())
+            disps[lo:lo + disp.shape[0]] = disp[:, 0] if disp.dim() == 4 else disp
+        for lo in range(0, R, chunk):
+            hi = min(lo + chunk, R)
+            a, b = max(lo - k, 0), min(hi + k, R)             # the chunk with its neighbours
+            local = table[a:b].copy()
+            local[local >= 0] -= a
+            local[:lo - a] = -1                                # the neighbours are sources only
+            local[hi - a:] = -1
+            res = ops.depth_consistency(disps[a:b], poses[a:b], K, inv_K, local, scale=tr.summary[6:7],
+                                        threshold=c["threshold"], min_views=c["min_views"], want_filtered=want_filtered,
+                                        backend=backend)
+            totals += res.counters[lo - a:hi - a].sum(0)
+            if want_filtered:
+                filtered[lo:hi] = res.filtered[lo - a:hi - a]
+    valid, visible, consistent, err_sum, kept = (int(v) for v in totals.cpu().tolist())      # the one read-back
+    share = lambda part, whole: part / whole if whole else float("nan")                      # noqa: E731
+    out = dict(c, frames=R, valid=valid, visible=visible, consistent=consistent, err_sum=err_sum, kept=kept,
+               mean_err=share(err_sum / 16777216.0, visible), agree_share=share(consistent, visible),
+               kept_share=share(kept, valid))
+    return out, filtered
 
 
 PLOT_GT, PLOT_PRED, PLOT_START, PLOT_BAR = (40, 40, 40), (214, 39, 40), (31, 119, 180), (0, 0, 0)

@@ -2003,6 +2003,79 @@ def map_finish(state, voxel, min_points=1, backend=None):
     return out_keys, vertices, out_counts, m
 
 
+# ---------------------------------------------------------------------------- depth-pose geometric consistency
+Consistency = collections.namedtuple("Consistency", "filtered seen agree err counters transforms")
+Consistency.__doc__ = """What `depth_consistency` leaves on the device: `filtered` float32 [n,h,w] or None, `seen` and
+`agree` uint8 [n,h,w], `err` float32 [n,h,w] or None, `counters` int64 [n,5] (valid pixels, visible samples, agreeing
+samples, the sum of err in units of 2^-24, pixels kept), `transforms` float64 [n,V,12]."""
+
+
+def _matrix33(m, what, dev):
+    m = m if torch.is_tensor(m) else torch.as_tensor(np.asarray(m, dtype=np.float32))
+    if m.dtype != torch.float32 or tuple(m.shape) != (3, 3):
+        raise ValueError("depth_consistency: %s must be float32 [3,3], got %s %s" % (what, m.dtype, tuple(m.shape)))
+    return upload(m.contiguous(), dev) if m.device != dev else m.contiguous()
+
+
+def depth_consistency(disp, poses, K, inv_K, sources, scale=None, threshold=0.05, min_views=1, is_depth=False,
+                      want_err=False, want_filtered=True, backend=None):
+    """`bbd_depth_consistency` (two launches, nothing read back): every pixel of every frame is back-projected with its
+    depth, moved into each of its source frames with the relative pose and compared with the depth that frame predicts
+    there, err = |z - d_b| / (z + d_b).  `disp` float32 [n,h,w] or [n,1,h,w], the scaled disparity (or,
+    `is_depth`, depth); `poses` float64 [n,4,4] or [n,16] camera to world; `K`, `inv_K` float32 [3,3] of the h x w map
+    (host or device); `sources` int32 [n,V] (host or device; `pointcloud.neighbour_sources`), -1 = none; `scale` None or
+    a float64 DEVICE tensor of one element, as `map_accumulate` takes it.  A pixel is kept in `filtered` when it is valid
+    and agrees (err < `threshold`, strict) in at least `min_views` sources.  Returns a `Consistency`."""
+    backend = backend or default_backend()
+    disp = disp.detach()
+    if disp.dim() == 4:
+        assert disp.shape[1] == 1
+        disp = disp[:, 0]
+    if disp.dim() != 3 or disp.dtype != torch.float32:
+        raise ValueError("depth_consistency: disp must be float32 [n,h,w] or [n,1,h,w], got %s %s"
+                         % (disp.dtype, tuple(disp.shape)))
+    n, h, w = disp.shape
+    poses = poses.detach()
+    if n < 1:
+        raise ValueError("depth_consistency: at least one frame is needed")
+    if poses.dtype != torch.float64 or poses.numel() != 16 * n or poses.shape[0] != n:
+        raise ValueError("depth_consistency: poses must be float64 [%d,4,4], got %s %s"
+                         % (n, poses.dtype, tuple(poses.shape)))
+    sources = sources if torch.is_tensor(sources) else torch.as_tensor(np.asarray(sources))
+    if sources.dtype != torch.int32 or sources.dim() != 2 or sources.shape[0] != n \
+            or not 1 <= sources.shape[1] <= _lib.CONSIST_MAX_VIEWS:
+        raise ValueError("depth_consistency: sources must be int32 [%d,V] with 1 <= V <= %d, got %s %s"
+                         % (n, _lib.CONSIST_MAX_VIEWS, sources.dtype, tuple(sources.shape)))
+    V = int(sources.shape[1])
+    threshold, min_views = float(threshold), int(min_views)
+    if not threshold >= 0.0:
+        raise ValueError("depth_consistency: the threshold must not be negative, got %r" % (threshold,))
+    if min_views < 0:
+        raise ValueError("depth_consistency: min_views must not be negative, got %d" % min_views)
+    if n * h * w > 0x7fffffff:
+        raise ValueError("depth_consistency: %d frames of %d x %d pixels are more than one call holds; split the batch"
+                         % (n, h, w))
+    dev = disp.device
+    disp, poses = disp.contiguous(), poses.contiguous()
+    K3, iK = _matrix33(K, "K", dev), _matrix33(inv_K, "inv_K", dev)
+    sources = upload(sources.contiguous(), dev) if sources.device != dev else sources.contiguous()
+    if scale is not None:
+        assert scale.dtype == torch.float64 and scale.numel() == 1 and scale.device == dev
+    backend._check(disp, poses, K3, iK, sources, scale)
+    transforms = torch.empty(n, V, 12, dtype=torch.float64, device=dev)
+    seen = torch.empty(n, h, w, dtype=torch.uint8, device=dev)
+    agree = torch.empty(n, h, w, dtype=torch.uint8, device=dev)
+    err = torch.empty(n, h, w, dtype=torch.float32, device=dev) if want_err else None
+    filtered = torch.empty(n, h, w, dtype=torch.float32, device=dev) if want_filtered else None
+    counters = torch.empty(n, _lib.CONSIST_COUNTERS, dtype=torch.int64, device=dev)
+    # `scale` may be a view into a larger tensor: its address is taken as it is
+    backend.run("bbd_depth_consistency", disp, ptr(disp), ptr(poses),
+                ctypes.c_void_p(0 if scale is None else scale.data_ptr()), ptr(K3), ptr(iK), ptr(sources), ptr(transforms),
+                ptr(seen), ptr(agree), ptr(err), ptr(filtered), ptr(counters), n, h, w, V, threshold, min_views,
+                _lib.CONSIST_INPUT_IS_DEPTH if is_depth else 0)
+    return Consistency(filtered, seen, agree, err, counters, transforms)
+
+
 # ---------------------------------------------------------------------------- views (rasterised points and polylines)
 ViewState = collections.namedtuple("ViewState", "cells counters H W")
 ViewState.__doc__ = """The caller-owned canvas of the `bbd_view_*` entries: `cells` int64 [H,W] (the uint64 keys, empty =

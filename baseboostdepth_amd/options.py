@@ -114,6 +114,20 @@ class MonodepthOptions:
         self.parser.add_argument("--map_min_points", type=int, default=1, help="drop voxels with fewer points")
         self.parser.add_argument("--map_capacity", type=int, default=1 << 24,
                                  help="slots of the voxel table (rounded up to a power of two, 48 bytes each)")
+        # depth-pose geometric consistency: the depth of a frame against the depth of its neighbours under the predicted
+        # motion.  The default threshold is a knob, not a finding: neither the score nor the filter has been
+        # measured on real KITTI predictions
+        self.parser.add_argument("--consistency", action="store_true",
+                                 help="with --trajectory: also print the mean depth-pose consistency error of the "
+                                      "sequence and the shares of samples that agree (--map_every is honoured)")
+        self.parser.add_argument("--consistency_views", type=int, default=1,
+                                 help="check every frame against its k neighbours on either side")
+        self.parser.add_argument("--consistency_threshold", type=float, default=0.05,
+                                 help="a sample agrees when |z - d| / (z + d) is below this (not calibrated)")
+        self.parser.add_argument("--consistency_min_views", type=int, default=1,
+                                 help="a pixel is kept when it agrees in at least this many neighbours")
+        self.parser.add_argument("--map_consistent", action="store_true",
+                                 help="with --save_map: fuse only the pixels the consistency check keeps")
         # the bird's-eye plot of the run: both trajectories over the scene map, drawn on the device
         self.parser.add_argument("--save_plot", type=str, default=None, metavar="FILE.png",
                                  help="with --trajectory: write a picture of the ground-truth and the aligned predicted "

@@ -7,6 +7,7 @@ bytes as they came from the device.  Nothing here touches a point.
 
 `SceneMap` fuses the clouds of many posed frames on a voxel grid (`ops.map_*`) and reads the finished
 voxels back once, as one array of the same vertex record.
+`neighbour_sources` makes the table of frames that `ops.depth_consistency` checks every frame against.
 
 `Canvas` draws such vertices, and polylines such as trajectories, into a picture on the device (`ops.view_*`, DESIGN.md
 6k); `ortho_view` and `orbit_view` make the view matrices it takes.
@@ -85,6 +86,17 @@ def intrinsics_at(inv_K, size, map_size):
     sx, sy = W0 / w, H0 / h
     A = np.array([[sx, 0.0, 0.5 * sx - 0.5], [0.0, sy, 0.5 * sy - 0.5], [0.0, 0.0, 1.0]], dtype=np.float64)
     return np.ascontiguousarray((inv_K[:3, :3] @ A).astype(np.float32))
+
+
+def neighbour_sources(n, offsets=(-1, 1)):
+    """The int32 [n, len(offsets)] source table of `ops.depth_consistency` for a run of n frames: frame i is checked
+    against frames i + o for every o of `offsets`, -1 (none) past the ends of the run."""
+    n, offsets = int(n), [int(o) for o in offsets]
+    if n < 1 or not offsets:
+        raise ValueError("neighbour_sources: at least one frame and one offset are needed, got %d and %r" % (n, offsets))
+    table = np.arange(n, dtype=np.int64)[:, None] + np.asarray(offsets, dtype=np.int64)[None, :]
+    table[(table < 0) | (table >= n)] = -1
+    return np.ascontiguousarray(table.astype(np.int32))
 
 
 def cloud_arrays(vertices, counts, offsets):

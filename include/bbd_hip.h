@@ -52,8 +52,9 @@ extern "C" {
  * 15 = bbd_point_cloud (coloured point clouds); 16 = bbd_map_* (voxel-fused scene map);
  * 17 = bbd_view_* (points and polylines rasterised into a z-buffered canvas);
  * 18 = bbd_ground_scale (metric scale of a prediction from the camera's height above the ground);
- * 19 = bbd_disp_head_fwd / _bwd (the disparity head with its sigmoid inside). */
-#define BBD_ABI_VERSION 19
+ * 19 = bbd_disp_head_fwd / _bwd (the disparity head with its sigmoid inside);
+ * 20 = bbd_depth_consistency (depth-pose geometric consistency: a score and a filter for the scene map). */
+#define BBD_ABI_VERSION 20
 
 /* Source frames live in separate tensors, one per frame id (inputs[("color", f, 0)],
  * trainer.py:428).  A "slot" indexes a host array of their base pointers. */
@@ -637,6 +638,56 @@ int bbd_map_accumulate(uint64_t* keys, uint64_t* pos, uint32_t* col, int64_t* co
 int bbd_map_finish(const uint64_t* keys, const uint64_t* pos, const uint32_t* col, int T, int min_points, double voxel,
                    int64_t* out_keys, void* vertices, int32_t* out_counts, int32_t* m, int32_t* scratch,
                    int scratch_ints, void* stream);
+
+/* ---- Depth-pose geometric consistency (csrc/bbd_consist.hip, ops.depth_consistency): does the depth of
+ * a frame agree with the depth of its neighbours under the predicted motion?  A pixel of reference frame i is
+ * back-projected with its depth, moved into source frame j with inv(P_j) . P_i and projected; the depth z it has there is
+ * compared with the depth d_b frame j predicts at that place: err = |z - d_b| / (z + d_b), in [0, 1].  One call, two
+ * launches (the pairs' transforms, then a lane per reference pixel), no scratch: every buffer is the caller's and its
+ * size is written here.
+ *   disp        float32 [n,h,w]: the network's scaled disparity (depth = 1 / disp), or, with
+ *               BBD_CONSIST_INPUT_IS_DEPTH, depth.  A value is VALID when its depth is above 0 and finite
+ *   poses       float64 [n,16] row-major 4x4, camera to world (the rows of bbd_pose_trajectory's aligned trajectory)
+ *   scale       DEVICE pointer to one double that multiplies depth and camera-frame point, or NULL = 1: the same meaning
+ *               as in bbd_map_accumulate
+ *   K, inv_K    float32 [3,3] row-major, of the h x w map
+ *   sources     int32 [n,V] on the device, 1 <= V <= BBD_CONSIST_MAX_VIEWS: row i lists the frames that frame i is
+ *               checked against, -1 = none.  The table lives on the device and cannot be checked on the host: an entry
+ *               outside [-1, n) is treated as -1
+ *   transforms  OUT float64 [n,V,12]: rows 0..2 of inv(P_src) . P_ref of every listed pair - the general inverse of the
+ *               odometry evaluation (Gauss-Jordan, partial pivoting), then the 4x4 product, each entry
+ *               ((a0 b0 + a1 b1) + a2 b2) + a3 b3; twelve zeros where there is no source.  Written by the first launch,
+ *               read by the second
+ *   seen        OUT uint8 [n,h,w]: the number of sources in which the pixel is visible
+ *   agree       OUT uint8 [n,h,w]: the number of sources in which it is visible and err < threshold (strict: threshold
+ *               0 keeps nothing)
+ *   err         OUT float32 [n,h,w] or NULL: the smallest err over the visible sources; none: the quiet NaN 0x7fc00000
+ *   filtered    OUT float32 [n,h,w] or NULL: disp where the pixel is VALID and agree >= min_views, else 0 - also under
+ *               the depth flag.  bbd_map_accumulate turns a disparity of 0 into an infinite depth and rejects it, so the
+ *               map takes `filtered` in the place of `disp` as it is
+ *   counters    OUT int64 [n,BBD_CONSIST_COUNTERS], cleared by the call: per frame {VALID pixels, visible samples,
+ *               agreeing samples, sum over visible samples of (int64)((double)err * 16777216.0 + 0.5), pixels kept}.
+ *               Integer sums: identical calls give identical bytes, whatever the launch geometry
+ * For pixel k = y * w + x of frame i (operation by operation: csrc/bbd_consist_math.h, -ffp-contract=off):
+ *   d = 1.0f / disp (or disp), float32;  p = bbd_syns_backproject(inv_K, k, h, w, pixel rays, d), float32 - the point the
+ *   scene map fuses;  q = scale * (double)p;  per source X = M q + t in float64, three-term sums left to right, z = X_2;
+ *   c = K X likewise, u = c_0 / c_2, t = c_1 / c_2.  The sample is VISIBLE when z > 0 and finite, 0 <= u <= w - 1,
+ *   0 <= t <= h - 1 and the four taps at x0 = min(floor(u), w - 2), y0 = min(floor(t), h - 2) are VALID (maps with h < 2
+ *   or w < 2 have no visible samples).  The INVERSE depth of the source is sampled bilinearly in float64,
+ *   s = top + fy (bot - top) with top = s00 + fx (s01 - s00) - it is affine in the pixel on a plane, depth is not -
+ *   d_b = scale / s (above 0 and finite, else not visible), err = (float)(fabs(z - d_b) / (z + d_b)).
+ * No transcendental function appears, so a correctly rounding host gives the device's bits.
+ *
+ * No allocation, no host synchronisation.  A NULL required pointer (all but scale, err and filtered), n, h, w or V below
+ * 1, V above BBD_CONSIST_MAX_VIEWS, min_views below 0, a negative or NaN threshold or an unknown flag bit return
+ * BBD_E_BADARG; n * h * w > INT_MAX returns BBD_E_TOOMANY.  Nothing is launched then. */
+#define BBD_CONSIST_INPUT_IS_DEPTH 1
+#define BBD_CONSIST_MAX_VIEWS 8
+#define BBD_CONSIST_COUNTERS 5
+int bbd_depth_consistency(const float* disp, const double* poses, const double* scale, const float* K,
+                          const float* inv_K, const int32_t* sources, double* transforms, uint8_t* seen, uint8_t* agree,
+                          float* err, float* filtered, int64_t* counters, int n, int h, int w, int V, double threshold,
+                          int min_views, int flags, void* stream);
 
 /* ---- Views (csrc/bbd_view.hip, pointcloud.Canvas): points and polylines rasterised into a z-buffered
  * canvas, resolved to RGB bytes.  The canvas is the caller's:
