@@ -28,6 +28,7 @@ constexpr int MAX_SPLIT = 64;
 #ifndef BN_SMALL_ELEMS
 #define BN_SMALL_ELEMS 8192     // per (channel, call group): at or below this the two passes of a direction share one launch
 #endif
+static_assert(BBD_STEM_MIN_ELEMS == BN_SMALL_ELEMS, "the stem takes exactly the activations of the two-launch form");
 
 struct BnArgs {
   const float* x;        // [N,C,HW] conv output
@@ -49,6 +50,12 @@ struct BnArgs {
   float* dbeta;
   int N, C, HW, split, relu;
   float eps, momentum;
+  // encoder stem (bbd_stem_*): MaxPool2d(3, 2, 1) of y fused into both directions.  W = row length of the HW plane;
+  // forward: y may be NULL, pooled / code [N,C,OH,OW] are written; backward: dy may be NULL, gpool / code are read
+  int W;
+  float* pooled;
+  uint8_t* code;
+  const float* gpool;
   // call groups: samples [rows[g], rows[g+1]) are normalised with their own statistics, as if each group had been
   // a separate call of the layer (one batched pass of a network that the reference calls G times); blockIdx.z = g
   int G;
@@ -229,7 +236,66 @@ __device__ __forceinline__ void apply_slice(const BnArgs& a, int c, int grp, int
   }
 }
 
+// ---- where the backward takes g from.  POOL = false: a load of dy.  POOL = true (the encoder stem, bbd_stem_bwd):
+// g = [dy, if given] + the gradient that MaxPool2d(3, 2, 1) of y hands back to the pixel, gathered from the pooled
+// gradients whose code points at it - the full-size gradient of the pool and its sum with dy are never written.
+// pool_grad4: the four pixels (h, w0 .. w0 + 3) of plane `pl`, w0 % 4 == 0 and W % 4 == 0, with the very expressions
+// (and association) of maxpool3s2_bwd_kernel's a, b (even rows) and c, d (odd rows), so the sums have its bits.
+__device__ __forceinline__ float4 pool_grad4(const BnArgs& a, size_t pl, int h, int w0) {
+  const int H = a.HW / a.W, OH = (H - 1) / 2 + 1, OW = a.W >> 1;
+  const int oy = h >> 1, ox = w0 >> 1;                        // ox is even, OW is even: ox + 1 < OW
+  const size_t r0 = (pl * OH + oy) * OW + ox;
+  const bool right = ox + 2 < OW;
+  const float2 g0 = *reinterpret_cast<const float2*>(a.gpool + r0);
+  const uchar2 k0 = *reinterpret_cast<const uchar2*>(a.code + r0);
+  const float g00 = g0.x, g01 = g0.y, g02 = right ? a.gpool[r0 + 2] : 0.0f;
+  const int c00 = k0.x, c01 = k0.y, c02 = right ? (int)a.code[r0 + 2] : -1;
+  float4 o;
+  if (!(h & 1)) {                                             // row 2 oy: window positions 4, 5 of (oy, .), 3 of (oy, . + 1)
+    o.x = c00 == 4 ? g00 : 0.0f;
+    o.y = (c00 == 5 ? g00 : 0.0f) + (c01 == 3 ? g01 : 0.0f);
+    o.z = c01 == 4 ? g01 : 0.0f;
+    o.w = (c01 == 5 ? g01 : 0.0f) + (c02 == 3 ? g02 : 0.0f);
+    return o;
+  }
+  const bool down = oy + 1 < OH;                              // row 2 oy + 1: positions 7, 8 of (oy, .), 1, 2 of (oy + 1, .)
+  float g10 = 0.0f, g11 = 0.0f, g12 = 0.0f;
+  int c10 = -1, c11 = -1, c12 = -1;
+  if (down) {
+    const float2 g1 = *reinterpret_cast<const float2*>(a.gpool + r0 + OW);
+    const uchar2 k1 = *reinterpret_cast<const uchar2*>(a.code + r0 + OW);
+    g10 = g1.x; g11 = g1.y; c10 = k1.x; c11 = k1.y;
+    if (right) { g12 = a.gpool[r0 + OW + 2]; c12 = a.code[r0 + OW + 2]; }
+  }
+  o.x = (c00 == 7 ? g00 : 0.0f) + (c10 == 1 ? g10 : 0.0f);
+  o.y = ((c00 == 8 ? g00 : 0.0f) + (c01 == 6 ? g01 : 0.0f)) + ((c10 == 2 ? g10 : 0.0f) + (c11 == 0 ? g11 : 0.0f));
+  o.z = (c01 == 7 ? g01 : 0.0f) + (c11 == 1 ? g11 : 0.0f);
+  o.w = ((c01 == 8 ? g01 : 0.0f) + (c02 == 6 ? g02 : 0.0f)) + ((c11 == 2 ? g11 : 0.0f) + (c12 == 0 ? g12 : 0.0f));
+  return o;
+}
+
+// g of the float4 at offset i (a multiple of 4) of plane (n, c); base = that plane's offset in x
+template <bool POOL>
+__device__ __forceinline__ float4 grad4(const BnArgs& a, int n, int c, size_t base, int i) {
+  if (!POOL) return *reinterpret_cast<const float4*>(a.dy + base + i);
+  const int h = i / a.W;
+  float4 g = pool_grad4(a, (size_t)n * a.C + c, h, i - h * a.W);
+  if (a.dy) {
+    const float4 t = *reinterpret_cast<const float4*>(a.dy + base + i);
+    g.x = t.x + g.x; g.y = t.y + g.y; g.z = t.z + g.z; g.w = t.w + g.w;
+  }
+  return g;
+}
+// one element (planes that are no multiple of 4 long: never the stem, whose rows are)
+template <bool POOL>
+__device__ __forceinline__ float grad1(const BnArgs& a, int n, int c, size_t base, int i) {
+  if (!POOL) return a.dy[base + i];
+  const float4 g = grad4<true>(a, n, c, base, i & ~3);
+  return (i & 3) == 0 ? g.x : (i & 3) == 1 ? g.y : (i & 3) == 2 ? g.z : g.w;
+}
+
 // backward reduction of slice k: block totals of g = dy * (y > 0) and g * xhat
+template <bool POOL>
 __device__ __forceinline__ void bwd_reduce_slice(const BnArgs& a, int c, int grp, int split, int k, double* sh, double* tg,
                                                  double* tgx) {
   int lo, hi;
@@ -246,7 +312,7 @@ __device__ __forceinline__ void bwd_reduce_slice(const BnArgs& a, int c, int grp
     float sg = 0.0f, sgx = 0.0f;
     if (vec) {
       for (int i = lo + 4 * lane; i < hi; i += 4 * 64) {
-        float4 g = *reinterpret_cast<const float4*>(a.dy + base + i);
+        float4 g = grad4<POOL>(a, n, c, base, i);
         const float4 x = *reinterpret_cast<const float4*>(a.x + base + i);
         if (a.relu) {
           float4 y;
@@ -265,7 +331,7 @@ __device__ __forceinline__ void bwd_reduce_slice(const BnArgs& a, int c, int grp
       }
     } else {
       for (int i = lo + lane; i < hi; i += 64) {
-        float g = a.dy[base + i];
+        float g = grad1<POOL>(a, n, c, base, i);
         if (a.relu && !((remask ? (a.x[base + i] - mean) * scale + shift : a.y[base + i]) > 0.0f)) g = 0.0f;
         sg += g;
         sgx += g * ((a.x[base + i] - mean) * invstd);
@@ -279,6 +345,7 @@ __device__ __forceinline__ void bwd_reduce_slice(const BnArgs& a, int c, int grp
 }
 
 // backward apply of slice k
+template <bool POOL>
 __device__ __forceinline__ void bwd_apply_slice(const BnArgs& a, int c, int grp, int split, int k, float mg, float mgx,
                                                 float kk) {
   const float mean = a.mean[(size_t)grp * a.C + c], invstd = a.invstd[(size_t)grp * a.C + c];
@@ -292,7 +359,7 @@ __device__ __forceinline__ void bwd_apply_slice(const BnArgs& a, int c, int grp,
     const size_t base = ((size_t)n * a.C + c) * a.HW;
     if (vec) {
       for (int i = lo + 4 * lane; i < hi; i += 4 * 64) {
-        float4 g = *reinterpret_cast<const float4*>(a.dy + base + i);
+        float4 g = grad4<POOL>(a, n, c, base, i);
         const float4 x = *reinterpret_cast<const float4*>(a.x + base + i);
         if (a.relu) {
           float4 y;
@@ -315,7 +382,7 @@ __device__ __forceinline__ void bwd_apply_slice(const BnArgs& a, int c, int grp,
       }
     } else {
       for (int i = lo + lane; i < hi; i += 64) {
-        float g = a.dy[base + i];
+        float g = grad1<POOL>(a, n, c, base, i);
         if (a.relu && !((remask ? (a.x[base + i] - mean) * scale + shift : a.y[base + i]) > 0.0f)) g = 0.0f;
         if (a.dres) a.dres[base + i] = g;
         a.dx[base + i] = kk * (g - mg - ((a.x[base + i] - mean) * invstd) * mgx);
@@ -372,19 +439,124 @@ __global__ __launch_bounds__(NT) void bn_apply_kernel(BnArgs a) {
   apply_slice(a, c, grp, split, blockIdx.x, s_mean, s_scale, s_shift);
 }
 
+// ---- encoder stem, forward: bn_stats_kernel as above, then apply + ReLU + MaxPool2d(3, 2, 1) in one pass.
+// W % 4 == 0, so OW = W / 2 and a float4 of a row holds the windows of two pooled columns but for the pixel to its left.
+// A task is a strip of 4 columns through STEM_TP pooled rows of one image: it loads input rows 2 p0 - 1 .. 2 p0 + 2 TP - 1
+// (all in flight together), owns the last 2 TP of them (the first is the halo, the previous tile's row, fetched a second
+// time through the cache) and walks down them.  Tasks are numbered image-major, then tile, then strip, so a wave's lanes
+// read and write runs of a row: float4 of x and y, float2 of pooled values, two code bytes.  The left neighbour's last
+// value comes from the lane below; a wave's first lane loads it.  Grid (task groups of the largest group, C, G).
+constexpr int STEM_TP = 4;
+
+__device__ __forceinline__ float stem_y(float v, float mean, float scale, float shift) {
+  const float o = (v - mean) * scale + shift;        // apply_slice's expression
+  return o > 0.0f ? o : 0.0f;
+}
+// maxpool3s2_fwd_kernel's rule: the first maximum in row-major window order, a NaN replaces the running maximum
+__device__ __forceinline__ void stem_take(float v, int pos, float* best, int* bc) {
+  if (*bc < 0 || v > *best || v != v) { *best = v; *bc = pos; }
+}
+
+__global__ __launch_bounds__(NT) void stem_apply_pool_kernel(BnArgs a) {
+  __shared__ float s_mean, s_scale, s_shift;
+  const int c = blockIdx.y, grp = blockIdx.z;
+  const int first = group_row(a, grp), rows = group_row(a, grp + 1) - first;
+  const int W = a.W, H = a.HW / W, OH = (H - 1) / 2 + 1, OW = W >> 1, CW = W >> 2;
+  const int tiles = (OH + STEM_TP - 1) / STEM_TP;
+  const long long tasks = (long long)rows * tiles * CW;
+  if (blockIdx.x > 0 && (long long)blockIdx.x * NT >= tasks) return;      // the grid is sized for the largest group
+  if (threadIdx.x == 0) {
+    double ts, tss, mean, var;
+    group_totals(a, c, grp, &ts, &tss);
+    group_moments(a, c, grp, ts, tss, &mean, &var);
+    const float invstd = (float)(1.0 / sqrt(var + (double)a.eps));
+    s_mean = (float)mean;
+    s_scale = a.gamma[c] * invstd;
+    s_shift = a.beta[c];
+    if (blockIdx.x == 0) {
+      a.mean[(size_t)grp * a.C + c] = (float)mean;
+      a.invstd[(size_t)grp * a.C + c] = invstd;
+      if (grp == 0) update_running(a, c, [&](int q, double* s0, double* s1) { group_totals(a, c, q, s0, s1); });
+    }
+  }
+  __syncthreads();
+  const float mean = s_mean, scale = s_scale, shift = s_shift;
+  const long long t = (long long)blockIdx.x * NT + threadIdx.x;
+  const bool live = t < tasks;
+  // a dead lane keeps in step with the wave (the exchange below) on the coordinates of task 0; it loads and stores nothing
+  const long long tt = live ? t : 0;
+  const int img = (int)(tt / ((long long)tiles * CW));
+  const int rem = (int)(tt - (long long)img * tiles * CW);
+  const int tile = rem / CW, strip = rem - tile * CW;
+  const int p0 = tile * STEM_TP, w0 = strip << 2;
+  const size_t pl = (size_t)(first + img) * a.C + c;
+  const float* xp = a.x + pl * a.HW;
+  constexpr int NR = 2 * STEM_TP + 1;
+  float4 v[NR];
+  float lf[NR];
+  const bool own_left = strip > 0 && (threadIdx.x & 63) == 0;
+#pragma unroll
+  for (int r = 0; r < NR; ++r) {
+    const int h = 2 * p0 - 1 + r;
+    const bool in = live && h >= 0 && h < H;
+    v[r] = in ? *reinterpret_cast<const float4*>(xp + (size_t)h * W + w0) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    lf[r] = (in && own_left) ? xp[(size_t)h * W + w0 - 1] : 0.0f;
+  }
+#pragma unroll
+  for (int r = 0; r < NR; ++r) {
+    v[r].x = stem_y(v[r].x, mean, scale, shift); v[r].y = stem_y(v[r].y, mean, scale, shift);
+    v[r].z = stem_y(v[r].z, mean, scale, shift); v[r].w = stem_y(v[r].w, mean, scale, shift);
+    const float below = __shfl_up(v[r].w, 1, 64);              // the strip to the left, when it is in this wave
+    lf[r] = own_left ? stem_y(lf[r], mean, scale, shift) : below;
+  }
+  if (!live) return;
+  if (a.y) {
+    float* yp = a.y + pl * a.HW;
+#pragma unroll
+    for (int r = 1; r < NR; ++r) {
+      const int h = 2 * p0 - 1 + r;
+      if (h < H) *reinterpret_cast<float4*>(yp + (size_t)h * W + w0) = v[r];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < STEM_TP; ++j) {
+    const int oy = p0 + j;
+    if (oy >= OH) break;
+    float b0 = -INFINITY, b1 = -INFINITY;
+    int k0 = -1, k1 = -1;
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy) {
+      const int h = 2 * oy - 1 + dy;
+      if (h < 0 || h >= H) continue;
+      const float4 q = v[2 * j + dy];
+      if (strip > 0) stem_take(lf[2 * j + dy], dy * 3, &b0, &k0);
+      stem_take(q.x, dy * 3 + 1, &b0, &k0);
+      stem_take(q.y, dy * 3 + 2, &b0, &k0);
+      stem_take(q.y, dy * 3, &b1, &k1);
+      stem_take(q.z, dy * 3 + 1, &b1, &k1);
+      stem_take(q.w, dy * 3 + 2, &b1, &k1);
+    }
+    const size_t o = (pl * OH + oy) * OW + 2 * strip;
+    *reinterpret_cast<float2*>(a.pooled + o) = make_float2(b0, b1);
+    *reinterpret_cast<uchar2*>(a.code + o) = make_uchar2((unsigned char)k0, (unsigned char)k1);
+  }
+}
+
+template <bool POOL>
 __global__ __launch_bounds__(NT) void bn_bwd_reduce_kernel(BnArgs a) {
   __shared__ double sh[4];
   const int c = blockIdx.y, grp = blockIdx.z;
   const int split = pick_split(group_row(a, grp + 1) - group_row(a, grp), a.HW);
   if ((int)blockIdx.x >= split) return;
   double tg, tgx;
-  bwd_reduce_slice(a, c, grp, split, blockIdx.x, sh, &tg, &tgx);
+  bwd_reduce_slice<POOL>(a, c, grp, split, blockIdx.x, sh, &tg, &tgx);
   if (threadIdx.x == 0) {
     a.part[(((size_t)c * a.G + grp) * a.split + blockIdx.x) * 2] = tg;
     a.part[(((size_t)c * a.G + grp) * a.split + blockIdx.x) * 2 + 1] = tgx;
   }
 }
 
+template <bool POOL>
 __global__ __launch_bounds__(NT) void bn_bwd_apply_kernel(BnArgs a) {
   __shared__ float s_k[3];
   const int c = blockIdx.y, grp = blockIdx.z;
@@ -409,7 +581,7 @@ __global__ __launch_bounds__(NT) void bn_bwd_apply_kernel(BnArgs a) {
     }
   }
   __syncthreads();
-  bwd_apply_slice(a, c, grp, split, blockIdx.x, s_k[0], s_k[1], s_k[2]);
+  bwd_apply_slice<POOL>(a, c, grp, split, blockIdx.x, s_k[0], s_k[1], s_k[2]);
 }
 
 // ---- one launch per direction for small activations: grid (1, C, G), the workgroup owns its whole (channel, group).
@@ -462,7 +634,7 @@ __global__ __launch_bounds__(NT) void bn_bwd_small_kernel(BnArgs a) {
   double tg = 0.0, tgx = 0.0;
   for (int k = 0; k < split; ++k) {
     double kg, kgx;
-    bwd_reduce_slice(a, c, grp, split, k, sh, &kg, &kgx);
+    bwd_reduce_slice<false>(a, c, grp, split, k, sh, &kg, &kgx);
     tg += kg; tgx += kgx;
   }
   if (threadIdx.x == 0) {
@@ -479,7 +651,7 @@ __global__ __launch_bounds__(NT) void bn_bwd_small_kernel(BnArgs a) {
     }
   }
   __syncthreads();
-  for (int k = 0; k < split; ++k) bwd_apply_slice(a, c, grp, split, k, s_k[0], s_k[1], s_k[2]);
+  for (int k = 0; k < split; ++k) bwd_apply_slice<false>(a, c, grp, split, k, s_k[0], s_k[1], s_k[2]);
 }
 __global__ __launch_bounds__(64) void bn_param_grad_small_kernel(BnArgs a) {
   const int c = blockIdx.x * 64 + threadIdx.x;
@@ -1141,8 +1313,8 @@ int launch_bn_bwd(BnArgs& a, int biggest, hipStream_t st) {
     return status();
   }
   const dim3 grid((unsigned)a.split, (unsigned)a.C, (unsigned)a.G);
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel, grid, dim3(NT), 0, st, a);
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, grid, dim3(NT), 0, st, a);
+  hipLaunchKernelGGL(bn_bwd_reduce_kernel<false>, grid, dim3(NT), 0, st, a);
+  hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, grid, dim3(NT), 0, st, a);
   return status();
 }
 void fill_fwd(BnArgs& a, const float* x, const float* residual, const float* gamma, const float* beta, float* y,
@@ -1223,6 +1395,127 @@ int bbd_bn_act_grouped_dev_bwd(const float* x, const float* y, const float* grad
            HW, relu);
   a.G = G; a.rows_dev = group_table;
   return launch_bn_bwd(a, max_group_rows, static_cast<hipStream_t>(stream));
+}
+
+// ---- encoder stem: conv1 -> bn1 + ReLU -> MaxPool2d(3, 2, 1).  Only the two-launch form exists (BBD_STEM_MIN_ELEMS)
+namespace {
+bool stem_shape_ok(int biggest, int N, int C, int H, int W) {
+  if (N <= 0 || C <= 0 || C > 65535 || H < 1 || W < 4 || (W & 3) || biggest < 1 || biggest > N) return false;
+  if ((long long)H * W > 0x7fffffffLL) return false;
+  return (long long)biggest * H * W > BN_SMALL_ELEMS;
+}
+bool aligned(const void* p, uintptr_t to) { return ((uintptr_t)p & (to - 1)) == 0; }
+
+int launch_stem_fwd(BnArgs& a, int biggest, int H, int W, hipStream_t st) {
+  a.split = pick_split(biggest, a.HW);
+  a.W = W;
+  hipLaunchKernelGGL(bn_stats_kernel, dim3((unsigned)a.split, (unsigned)a.C, (unsigned)a.G), dim3(NT), 0, st, a);
+  const int OH = (H - 1) / 2 + 1;
+  const long long tasks = (long long)biggest * ((OH + STEM_TP - 1) / STEM_TP) * (W >> 2);
+  const long long groups = (tasks + NT - 1) / NT;
+  if (groups > 0x7fffffffLL) return BBD_E_BADARG;
+  hipLaunchKernelGGL(stem_apply_pool_kernel, dim3((unsigned)groups, (unsigned)a.C, (unsigned)a.G), dim3(NT), 0, st, a);
+  return status();
+}
+int launch_stem_bwd(BnArgs& a, int biggest, int W, hipStream_t st) {
+  a.split = pick_split(biggest, a.HW);
+  a.W = W;
+  const dim3 grid((unsigned)a.split, (unsigned)a.C, (unsigned)a.G);
+  if (a.gpool) {
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel<true>, grid, dim3(NT), 0, st, a);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, grid, dim3(NT), 0, st, a);
+  } else {                                   // the pool's output was not used: the plain backward on grad_y
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel<false>, grid, dim3(NT), 0, st, a);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, grid, dim3(NT), 0, st, a);
+  }
+  return status();
+}
+bool stem_fwd_ptrs_ok(const float* x, const float* gamma, const float* beta, const float* y, const float* pooled,
+                      const uint8_t* code, const float* save_mean, const float* save_invstd, const float* running_mean,
+                      const float* running_var, const double* scratch) {
+  if (!x || !gamma || !beta || !pooled || !code || !save_mean || !save_invstd || !scratch) return false;
+  if ((running_mean == nullptr) != (running_var == nullptr)) return false;
+  return aligned(x, 16) && aligned(y, 16) && aligned(pooled, 8) && aligned(code, 2);
+}
+bool stem_bwd_ptrs_ok(const float* x, const float* grad_y, const float* grad_pooled, const uint8_t* code, const float* gamma,
+                      const float* beta, const float* save_mean, const float* save_invstd, const float* grad_x,
+                      const float* grad_gamma, const float* grad_beta, const double* scratch) {
+  if (!x || !gamma || !beta || !save_mean || !save_invstd || !grad_x || !grad_gamma || !grad_beta || !scratch) return false;
+  if (!grad_y && !grad_pooled) return false;
+  if (grad_pooled && !code) return false;
+  return aligned(x, 16) && aligned(grad_y, 16) && aligned(grad_x, 16) && aligned(grad_pooled, 8) && aligned(code, 2);
+}
+void fill_stem_bwd(BnArgs& a, const float* x, const float* grad_y, const float* grad_pooled, const uint8_t* code,
+                   const float* gamma, const float* beta, const float* save_mean, const float* save_invstd, float* grad_x,
+                   float* grad_gamma, float* grad_beta, double* scratch, int N, int C, int H, int W) {
+  // y = NULL: the ReLU mask is re-derived from x, as in the backward of a forward without a residual
+  fill_bwd(a, x, nullptr, grad_y, gamma, beta, save_mean, save_invstd, grad_x, nullptr, grad_gamma, grad_beta, scratch, N, C,
+           H * W, 1);
+  a.gpool = grad_pooled;
+  a.code = const_cast<uint8_t*>(code);
+}
+}  // namespace
+
+int bbd_stem_fwd(const float* x, const float* gamma, const float* beta, float* y, float* pooled, uint8_t* code,
+                 float* save_mean, float* save_invstd, float* running_mean, float* running_var,
+                 long long* num_batches_tracked, double* scratch, const int32_t* group_rows, int G, int untracked_groups,
+                 int N, int C, int H, int W, double eps, double momentum, void* stream) {
+  if (!stem_fwd_ptrs_ok(x, gamma, beta, y, pooled, code, save_mean, save_invstd, running_mean, running_var, scratch))
+    return BBD_E_BADARG;
+  if (untracked_groups < 0 || untracked_groups >= G) return BBD_E_BADARG;
+  BnArgs a = {};
+  const int biggest = fill_groups(group_rows, G, N, &a);
+  if (!biggest || !stem_shape_ok(biggest, N, C, H, W)) return BBD_E_BADARG;
+  fill_fwd(a, x, nullptr, gamma, beta, y, save_mean, save_invstd, running_mean, running_var, num_batches_tracked, scratch, N, C,
+           H * W, eps, momentum, 1);
+  a.untracked = untracked_groups;
+  a.pooled = pooled; a.code = code;
+  return launch_stem_fwd(a, biggest, H, W, static_cast<hipStream_t>(stream));
+}
+
+int bbd_stem_bwd(const float* x, const float* grad_y, const float* grad_pooled, const uint8_t* code, const float* gamma,
+                 const float* beta, const float* save_mean, const float* save_invstd, float* grad_x, float* grad_gamma,
+                 float* grad_beta, double* scratch, const int32_t* group_rows, int G, int N, int C, int H, int W,
+                 void* stream) {
+  if (!stem_bwd_ptrs_ok(x, grad_y, grad_pooled, code, gamma, beta, save_mean, save_invstd, grad_x, grad_gamma, grad_beta,
+                        scratch))
+    return BBD_E_BADARG;
+  BnArgs a = {};
+  const int biggest = fill_groups(group_rows, G, N, &a);
+  if (!biggest || !stem_shape_ok(biggest, N, C, H, W)) return BBD_E_BADARG;
+  fill_stem_bwd(a, x, grad_y, grad_pooled, code, gamma, beta, save_mean, save_invstd, grad_x, grad_gamma, grad_beta, scratch,
+                N, C, H, W);
+  return launch_stem_bwd(a, biggest, W, static_cast<hipStream_t>(stream));
+}
+
+int bbd_stem_dev_fwd(const float* x, const float* gamma, const float* beta, float* y, float* pooled, uint8_t* code,
+                     float* save_mean, float* save_invstd, float* running_mean, float* running_var,
+                     long long* num_batches_tracked, double* scratch, const int32_t* group_table, int G,
+                     int max_group_rows, int N, int C, int H, int W, double eps, double momentum, void* stream) {
+  if (!stem_fwd_ptrs_ok(x, gamma, beta, y, pooled, code, save_mean, save_invstd, running_mean, running_var, scratch))
+    return BBD_E_BADARG;
+  if (!group_table || G < 1 || G > BBD_BN_MAX_GROUPS || !stem_shape_ok(max_group_rows, N, C, H, W)) return BBD_E_BADARG;
+  BnArgs a = {};
+  fill_fwd(a, x, nullptr, gamma, beta, y, save_mean, save_invstd, running_mean, running_var, num_batches_tracked, scratch, N, C,
+           H * W, eps, momentum, 1);
+  a.G = G; a.rows_dev = group_table;
+  a.pooled = pooled; a.code = code;
+  return launch_stem_fwd(a, max_group_rows, H, W, static_cast<hipStream_t>(stream));
+}
+
+int bbd_stem_dev_bwd(const float* x, const float* grad_y, const float* grad_pooled, const uint8_t* code, const float* gamma,
+                     const float* beta, const float* save_mean, const float* save_invstd, float* grad_x, float* grad_gamma,
+                     float* grad_beta, double* scratch, const int32_t* group_table, int G, int max_group_rows, int N, int C,
+                     int H, int W, void* stream) {
+  if (!stem_bwd_ptrs_ok(x, grad_y, grad_pooled, code, gamma, beta, save_mean, save_invstd, grad_x, grad_gamma, grad_beta,
+                        scratch))
+    return BBD_E_BADARG;
+  if (!group_table || G < 1 || G > BBD_BN_MAX_GROUPS || !stem_shape_ok(max_group_rows, N, C, H, W)) return BBD_E_BADARG;
+  BnArgs a = {};
+  fill_stem_bwd(a, x, grad_y, grad_pooled, code, gamma, beta, save_mean, save_invstd, grad_x, grad_gamma, grad_beta, scratch,
+                N, C, H, W);
+  a.G = G; a.rows_dev = group_table;
+  return launch_stem_bwd(a, max_group_rows, W, static_cast<hipStream_t>(stream));
 }
 
 int bbd_bn_act_fwd(const float* x, const float* residual, const float* gamma, const float* beta, float* y,

@@ -145,14 +145,31 @@ class ResnetEncoder(nn.Module):
         self.encoder = ResNetTrunk(num_layers, num_input_images)
         if num_layers > 34:
             self.num_ch_enc[1:] *= 4
+        # False: nobody reads the stem's full-resolution feature (the pose network: only features[-1] reaches
+        # PoseDecoder) - forward returns None in its place and the fused stem does not write it
+        self.stem_feature = True
+
+    def _stem(self, x):
+        """conv1's output -> (f0 or None, pooled f0): one fused op where the library takes the activation
+        (`ops.stem_bn_relu_pool`), else bn1 + ReLU and the max-pool as two."""
+        e = self.encoder
+        bn = e.bn1
+        if (isinstance(bn, FusedBatchNorm2d) and isinstance(e.maxpool, MaxPool3s2) and bn.fused and x.is_cuda and bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None
+                and x.dtype == torch.float32 and x.dim() == 4 and x.shape[0] * x.shape[1] <= 65535):
+            from .. import ops
+            if ops.FUSED_NN and ops.FUSED_STEM and ops.stem_supported(x, ops._stem_rows(x.shape[0])):
+                return ops.stem_bn_relu_pool(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps,
+                                             want_y=self.stem_feature, num_batches_tracked=bn.num_batches_tracked)
+        f0 = bn(x, relu=True)
+        return (f0 if self.stem_feature else None), e.maxpool(f0)
 
     def forward(self, input_image, normalized=False):
         """`normalized`: the caller hands in `(image - 0.45) / 0.225` already (the pooled step's pair gather does it in the
         same pass, `ops.gather_pairs`)."""
         e = self.encoder
         x = input_image if normalized else (input_image - 0.45) / 0.225
-        f0 = e.bn1(e.conv1(x), relu=True)
-        f1 = e.layer1(e.maxpool(f0))
+        f0, pooled = self._stem(e.conv1(x))
+        f1 = e.layer1(pooled)
         f2 = e.layer2(f1)
         f3 = e.layer3(f2)
         f4 = e.layer4(f3)

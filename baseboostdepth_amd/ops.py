@@ -1389,6 +1389,97 @@ def maxpool3s2(x, backend=None):
     return _MaxPool3s2.apply(x, backend or default_backend())
 
 
+# ---------------------------------------------------------------------------- encoder stem: bn1 + ReLU + max-pool
+FUSED_STEM = os.environ.get("BBD_FUSED_STEM", "1") != "0"   # 0: batch_norm_act then maxpool3s2, as before (A/B runs)
+
+
+def stem_supported(x, rows):
+    """Does `bbd_stem_*` take activation `x` [N,C,H,W] whose largest call group has `rows` samples?  (The library's own
+    condition: the two-launch BatchNorm form and rows of whole float4s; it refuses everything else.)"""
+    return (x.dim() == 4 and x.dtype == torch.float32 and x.shape[3] % 4 == 0 and x.shape[2] >= 1
+            and 1 <= rows <= x.shape[0] and x.shape[1] <= 65535
+            and rows * x.shape[2] * x.shape[3] > _lib.STEM_MIN_ELEMS)
+
+
+def _stem_rows(N):
+    """largest call group of the batched pass being run"""
+    if _bn_device is not None:
+        return _bn_device[2]
+    return max(_bn_groups) if _bn_groups is not None else N
+
+
+class _StemBnReluPool(torch.autograd.Function):
+    """`maxpool3s2(batch_norm_act(x, ..., relu=True))` with the pool inside the BatchNorm launches (csrc/bbd_nn.hip,
+    bbd_stem_*): two launches each way, y written only on request, no full-size gradient of the pool."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, batches, momentum, eps, want_y, backend):
+        x = x.contiguous()
+        N, C, H, W = x.shape
+        backend._check(x, weight, bias, running_mean, running_var)
+        OH, OW = (H - 1) // 2 + 1, W // 2
+        y = torch.empty_like(x) if want_y else None
+        pooled = torch.empty(N, C, OH, OW, device=x.device, dtype=torch.float32)
+        code = torch.empty(N, C, OH, OW, device=x.device, dtype=torch.uint8)
+        if _bn_device is not None:
+            table, G, biggest = _bn_device
+            assert _bn_groups is None and biggest <= N
+            rows = (table, G, biggest)
+        else:
+            rows = _bn_groups if _bn_groups is not None else [N]
+            assert sum(rows) == N, "ops.bn_call_groups does not describe this batch (%s vs %d rows)" % (rows, N)
+            G, biggest = len(rows), max(rows)
+        mean = torch.empty(G, C, device=x.device, dtype=torch.float32)
+        invstd = torch.empty(G, C, device=x.device, dtype=torch.float32)
+        scratch = torch.empty(backend.lib.bn_grouped_scratch_doubles(biggest, G, C, H * W), device=x.device,
+                              dtype=torch.float64)
+        if isinstance(rows, tuple):
+            backend.run("bbd_stem_dev_fwd", x, ptr(x), ptr(weight), ptr(bias), ptr(y), ptr(pooled), ptr(code), ptr(mean),
+                        ptr(invstd), ptr(running_mean), ptr(running_var), ptr(batches), ptr(scratch), ptr(rows[0]), G,
+                        biggest, N, C, H, W, float(eps), float(momentum))
+        else:
+            backend.run("bbd_stem_fwd", x, ptr(x), ptr(weight), ptr(bias), ptr(y), ptr(pooled), ptr(code), ptr(mean),
+                        ptr(invstd), ptr(running_mean), ptr(running_var), ptr(batches), ptr(scratch), _group_table(rows), G,
+                        _bn_untracked if _bn_groups is not None else 0, N, C, H, W, float(eps), float(momentum))
+        ctx.save_for_backward(x, code, weight, bias, mean, invstd)
+        ctx.meta = (backend, rows)
+        ctx.set_materialize_grads(False)
+        return y, pooled
+
+    @staticmethod
+    def backward(ctx, grad_y, grad_pooled):
+        x, code, weight, bias, mean, invstd = ctx.saved_tensors
+        backend, rows = ctx.meta
+        N, C, H, W = x.shape
+        grad_y = grad_y.contiguous() if grad_y is not None else None
+        grad_pooled = grad_pooled.contiguous() if grad_pooled is not None else None
+        grad_x = torch.empty_like(x)
+        grad_w = torch.empty(C, device=x.device, dtype=torch.float32)
+        grad_b = torch.empty(C, device=x.device, dtype=torch.float32)
+        if isinstance(rows, tuple):
+            table, G, biggest = rows
+            scratch = torch.empty(backend.lib.bn_grouped_scratch_doubles(biggest, G, C, H * W), device=x.device,
+                                  dtype=torch.float64)
+            backend.run("bbd_stem_dev_bwd", x, ptr(x), ptr(grad_y), ptr(grad_pooled), ptr(code), ptr(weight), ptr(bias),
+                        ptr(mean), ptr(invstd), ptr(grad_x), ptr(grad_w), ptr(grad_b), ptr(scratch), ptr(table), G, biggest,
+                        N, C, H, W)
+        else:
+            G = len(rows)
+            scratch = torch.empty(backend.lib.bn_grouped_scratch_doubles(max(rows), G, C, H * W), device=x.device,
+                                  dtype=torch.float64)
+            backend.run("bbd_stem_bwd", x, ptr(x), ptr(grad_y), ptr(grad_pooled), ptr(code), ptr(weight), ptr(bias),
+                        ptr(mean), ptr(invstd), ptr(grad_x), ptr(grad_w), ptr(grad_b), ptr(scratch), _group_table(rows), G,
+                        N, C, H, W)
+        return grad_x, grad_w, grad_b, None, None, None, None, None, None, None
+
+
+def stem_bn_relu_pool(x, weight, bias, running_mean, running_var, momentum, eps, want_y=True, backend=None,
+                      num_batches_tracked=None):
+    """The encoder stem's `bn1 + ReLU` and `MaxPool2d(3, 2, 1)` -> (y or None, pooled); see `stem_supported`."""
+    return _StemBnReluPool.apply(x, weight, bias, running_mean, running_var, num_batches_tracked, momentum, eps,
+                                 bool(want_y), backend or default_backend())
+
+
 # ---------------------------------------------------------------------------- decoder glue
 class _UpCatPad(torch.autograd.Function):
     """ReflectionPad2d(1)(cat(nearest_x2(x), skip)) in one pass each way (decoder glue, csrc/bbd_nn.hip)."""

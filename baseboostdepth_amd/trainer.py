@@ -70,6 +70,8 @@ class Trainer:
             self.models["depth"] = networks.DepthDecoder(self.models["encoder"].num_ch_enc, opt.scales)
         self.models["pose_encoder"] = networks.ResnetEncoder(18, opt.weights_init == "pretrained",
                                                              num_input_images=self.num_pose_frames)
+        if isinstance(self.models["pose_encoder"], networks.ResnetEncoder):
+            self.models["pose_encoder"].stem_feature = False     # PoseDecoder reads features[-1] only
         self.models["pose"] = networks.PoseDecoder(self.models["pose_encoder"].num_ch_enc,
                                                    num_input_features=1, num_frames_to_predict_for=2)
         for name in ("encoder", "depth", "pose_encoder", "pose"):

@@ -53,8 +53,9 @@ extern "C" {
  * 17 = bbd_view_* (points and polylines rasterised into a z-buffered canvas);
  * 18 = bbd_ground_scale (metric scale of a prediction from the camera's height above the ground);
  * 19 = bbd_disp_head_fwd / _bwd (the disparity head with its sigmoid inside);
- * 20 = bbd_depth_consistency (depth-pose geometric consistency: a score and a filter for the scene map). */
-#define BBD_ABI_VERSION 20
+ * 20 = bbd_depth_consistency (depth-pose geometric consistency: a score and a filter for the scene map);
+ * 21 = bbd_stem_* (the encoder stem: BatchNorm + ReLU + max-pool in one pass each way). */
+#define BBD_ABI_VERSION 21
 
 /* Source frames live in separate tensors, one per frame id (inputs[("color", f, 0)],
  * trainer.py:428).  A "slot" indexes a host array of their base pointers. */
@@ -903,6 +904,37 @@ int bbd_reflect_pad1_bwd(const float* grad_out, float* grad_in, int planes, int 
 int bbd_maxpool3s2_fwd(const float* in, float* out, uint8_t* code, int planes, int H, int W, void* stream);
 int bbd_maxpool3s2_bwd(const float* grad_out, const uint8_t* code, float* grad_in, int planes, int H, int W,
                        void* stream);
+
+/* Encoder stem (ABI 21): conv1 -> BatchNorm2d + ReLU -> MaxPool2d(3, 2, 1) (networks/resnet_encoder.py:80-84) with the
+ * pool inside the BatchNorm launches - what bbd_bn_act_grouped_fwd(relu = 1, no residual) followed by bbd_maxpool3s2_fwd
+ * computes, and the backward of that pair, bit for bit.
+ *   fwd: bn_stats, then ONE pass that reads x [N,C,H,W] and writes pooled / code [N,C,OH,OW] (OH = (H-1)/2+1, OW = W/2)
+ *        and, when y is not NULL, y [N,C,H,W]; statistics, running statistics and call groups as in
+ *        bbd_bn_act_grouped_fwd (save_mean / save_invstd [G,C]).
+ *   bwd: the two BatchNorm launches with g = [grad_y, if given] + the pooled gradients whose code points at the pixel;
+ *        neither the pool's full-size gradient nor its sum with grad_y is written.  grad_y or grad_pooled may be NULL,
+ *        not both; the ReLU mask is re-derived from x (`beta`).
+ * Only activations that take the two-launch form are accepted: largest group * H * W > BBD_STEM_MIN_ELEMS and
+ * W % 4 == 0 (any H >= 1); everything else is BBD_E_BADARG and stays with the separate entry points.  x, y and the
+ * full-size gradients are 16-byte aligned, pooled / grad_pooled 8, code 2.  scratch: bbd_bn_grouped_scratch_doubles(largest
+ * group, G, C, H * W).  The _dev_ forms read the device-resident table of bbd_bn_act_grouped_dev_*. */
+#define BBD_STEM_MIN_ELEMS 8192
+int bbd_stem_fwd(const float* x, const float* gamma, const float* beta, float* y, float* pooled, uint8_t* code,
+                 float* save_mean, float* save_invstd, float* running_mean, float* running_var,
+                 long long* num_batches_tracked, double* scratch, const int32_t* group_rows, int G, int untracked_groups,
+                 int N, int C, int H, int W, double eps, double momentum, void* stream);
+int bbd_stem_bwd(const float* x, const float* grad_y, const float* grad_pooled, const uint8_t* code, const float* gamma,
+                 const float* beta, const float* save_mean, const float* save_invstd, float* grad_x, float* grad_gamma,
+                 float* grad_beta, double* scratch, const int32_t* group_rows, int G, int N, int C, int H, int W,
+                 void* stream);
+int bbd_stem_dev_fwd(const float* x, const float* gamma, const float* beta, float* y, float* pooled, uint8_t* code,
+                     float* save_mean, float* save_invstd, float* running_mean, float* running_var,
+                     long long* num_batches_tracked, double* scratch, const int32_t* group_table, int G,
+                     int max_group_rows, int N, int C, int H, int W, double eps, double momentum, void* stream);
+int bbd_stem_dev_bwd(const float* x, const float* grad_y, const float* grad_pooled, const uint8_t* code, const float* gamma,
+                     const float* beta, const float* save_mean, const float* save_invstd, float* grad_x, float* grad_gamma,
+                     float* grad_beta, double* scratch, const int32_t* group_table, int G, int max_group_rows, int N, int C,
+                     int H, int W, void* stream);
 
 /* Disparity head of the depth decoder: layers.Conv3x3(C, 1) = ReflectionPad2d(1) + Conv2d(C, 1, 3) + bias
  * (layers.py:118-133, networks/depth_decoder.py:38-39), forward and backward without a padded copy.
