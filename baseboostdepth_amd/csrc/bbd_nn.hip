@@ -825,6 +825,314 @@ __global__ __launch_bounds__(64) void bias_grad_final_kernel(const double* __res
   gbias[c] = (float)s;
 }
 
+// ---- decoder glue with the ConvBlock's bias + ELU inside (bbd_upcat_pad_act_*, bbd_bias_elu_pad_*) -------------------
+// A decoder level is conv -> bias + ELU -> up-sample + concat + pad -> conv -> bias + ELU -> pad (the next level's).  The
+// separate passes above move every convolution output through HBM once more for the activation and again for the copy
+// into the next padded input; here the activation rides on the copy.  Numbers are those of the composition: the same
+// ELU expression, pad1_adjoint's row / centre / left / right order, the (a + b) + (c + d) block sum, g * (y + 1.0f).
+//
+// All four kernels are driven by the UN-padded rows: a wave owns one source row (several short ones: glue_row below), reads it with 16-byte accesses and
+// writes (forward) or gathers (backward) the one to three padded rows that mirror it.  A padded row starts 8-byte
+// aligned (its pitch W + 2 is even) and its interior one float later, so the padded side moves 16 bytes per lane at
+// 4-byte alignment - global accesses wider than a dword need dword alignment only - and the two border columns are
+// single stores / loads of the lanes that hold columns 1 and W - 2.  Rows that are no multiple of four floats long (or
+// whose tensors are not 16-byte aligned) take one element per lane.
+struct __attribute__((packed, aligned(4))) F4U { float x, y, z, w; };     // four floats at float alignment
+
+__device__ __forceinline__ float elu1(float v) { return v > 0.0f ? v : expm1f(v); }                  // bias_elu_fwd_kernel's
+__device__ __forceinline__ float elu1_grad(float g, float y) { return y > 0.0f ? g : g * (y + 1.0f); }   // bias_elu_bwd_kernel's
+
+// image columns x0 .. x0 + 3 of one unpadded row into a padded row: the interior, and the border column that mirrors
+// column 1 / W - 2 where the run holds it.  x0 % 4 == 0, W % 4 == 0.
+__device__ __forceinline__ void pad_row_store4(float* __restrict__ prow, int x0, int W, const float4& v) {
+  F4U o; o.x = v.x; o.y = v.y; o.z = v.z; o.w = v.w;
+  *reinterpret_cast<F4U*>(prow + x0 + 1) = o;
+  if (x0 == 0) prow[0] = v.y;
+  if (x0 + 4 == W) prow[W + 1] = v.z;
+}
+__device__ __forceinline__ void pad_row_store1(float* __restrict__ prow, int x, int W, float v) {
+  prow[x + 1] = v;
+  if (x == 1) prow[0] = v;
+  if (x == W - 2) prow[W + 1] = v;
+}
+
+// pad1_adjoint for K = 4 or 8 neighbouring columns x0 .. x0 + K - 1 of image row y (x0 % K == 0, W % K == 0): per
+// column the additions of pad1_adjoint in its order, the centre terms fetched as 16-byte runs.
+template <int K>
+__device__ __forceinline__ void pad1_adjoint_row(const float* __restrict__ row, int x0, int W, float (&acc)[K]) {
+  float m[K];
+#pragma unroll
+  for (int v = 0; v < K / 4; ++v) {
+    const F4U t = *reinterpret_cast<const F4U*>(row + x0 + 1 + 4 * v);
+    m[4 * v] = t.x; m[4 * v + 1] = t.y; m[4 * v + 2] = t.z; m[4 * v + 3] = t.w;
+  }
+#pragma unroll
+  for (int e = 0; e < K; ++e) {
+    acc[e] += m[e];
+    if (x0 + e == 1) acc[e] += row[0];
+    if (x0 + e == W - 2) acc[e] += row[W + 1];
+  }
+}
+template <int K>
+__device__ __forceinline__ void pad1_adjoint_run(const float* __restrict__ g, int y, int x0, int H, int W, float (&acc)[K]) {
+  const int PW = W + 2;
+#pragma unroll
+  for (int e = 0; e < K; ++e) acc[e] = 0.0f;
+  pad1_adjoint_row<K>(g + (size_t)(y + 1) * PW, x0, W, acc);
+  if (y == 1) pad1_adjoint_row<K>(g, x0, W, acc);
+  if (y == H - 2) pad1_adjoint_row<K>(g + (size_t)(H + 1) * PW, x0, W, acc);
+}
+
+// block total of a 64 x RR workgroup (threadIdx.y = wave); every thread of the block calls it
+__device__ __forceinline__ double block_sum_rows(double v, double* sh) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  if (threadIdx.x == 0) sh[threadIdx.y] = v;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+static_assert(RR == 4 && RR == BBD_GLUE_ROWS, "block_sum_rows adds four waves; the partial count is the header's");
+
+// Short rows: the decoder's coarse levels have rows of 20 or 40 floats - five or ten lanes' worth of float4s.  A wave
+// then takes 64 >> lg rows at once with 1 << lg lanes along each (lg chosen by the host from the row length, 6 = the
+// whole wave along one row); shifts and masks only.  A workgroup covers RR << (6 - lg) consecutive rows.
+__device__ __forceinline__ int glue_row(int lg) { return ((blockIdx.x * RR + threadIdx.y) << (6 - lg)) + (threadIdx.x >> lg); }
+__device__ __forceinline__ int glue_lane(int lg) { return threadIdx.x & ((1 << lg) - 1); }
+
+// out = ReflectionPad2d(1)(cat(nearest_x2(ELU(z + bias)), skip)).  Source row i of z is image rows 2i, 2i + 1 = padded
+// rows 2i + 1, 2i + 2, and also padded row 0 (i = 0) and 2h + 1 (i = h - 1); the activation is computed once per element.
+__global__ __launch_bounds__(RW * RR) void upcat_pad_act_fwd_kernel(const float* __restrict__ z, const float* __restrict__ bias,
+                                                                    const float* __restrict__ skip, float* __restrict__ out,
+                                                                    int C1, int C2, int h, int w, int vec_z, int vec_skip, int lg_z,
+                                                                    int lg_skip) {
+  const int H = 2 * h, W = 2 * w, PH = H + 2, PW = W + 2;
+  const int pl = blockIdx.y, n = pl / (C1 + C2), c = pl - n * (C1 + C2);
+  float* dst = out + (size_t)pl * PH * PW;
+  if (c < C1) {
+    const int i = glue_row(lg_z);
+    if (i >= h) return;
+    const float b = bias[c];
+    const float* src = z + (((size_t)n * C1 + c) * h + i) * w;
+    int rows[4], nr = 0;                     // the padded rows that show source row i (offsets: a plane is below 2^31)
+    rows[nr++] = (2 * i + 1) * PW;
+    rows[nr++] = (2 * i + 2) * PW;
+    if (i == 0) rows[nr++] = 0;
+    if (i == h - 1) rows[nr++] = (H + 1) * PW;
+    if (vec_z) {
+      for (int j0 = 4 * glue_lane(lg_z); j0 < w; j0 += 4 << lg_z) {
+        float4 a = *reinterpret_cast<const float4*>(src + j0);
+        a.x = elu1(a.x + b); a.y = elu1(a.y + b); a.z = elu1(a.z + b); a.w = elu1(a.w + b);
+        F4U lo, hi;
+        lo.x = a.x; lo.y = a.x; lo.z = a.y; lo.w = a.y;
+        hi.x = a.z; hi.y = a.z; hi.z = a.w; hi.w = a.w;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          if (r < nr) {
+            float* p = dst + rows[r];
+            *reinterpret_cast<F4U*>(p + 2 * j0 + 1) = lo;
+            *reinterpret_cast<F4U*>(p + 2 * j0 + 5) = hi;
+            if (j0 == 0) p[0] = a.x;
+            if (j0 + 4 == w) p[PW - 1] = a.w;
+          }
+        }
+      }
+    } else {
+      for (int j = glue_lane(lg_z); j < w; j += 1 << lg_z) {
+        const float a = elu1(src[j] + b);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          if (r < nr) {
+            float* p = dst + rows[r];
+            p[2 * j + 1] = a;
+            p[2 * j + 2] = a;
+            if (j == 0) p[0] = a;
+            if (j == w - 1) p[PW - 1] = a;
+          }
+        }
+      }
+    }
+  } else {
+    for (int y = glue_row(lg_skip); y < H; y += (gridDim.x * RR) << (6 - lg_skip)) {
+      const float* src = skip + (((size_t)n * C2 + (c - C1)) * H + y) * W;
+      float* mid = dst + (size_t)(y + 1) * PW;
+      float* top = y == 1 ? dst : nullptr;
+      float* bot = y == H - 2 ? dst + (size_t)(H + 1) * PW : nullptr;
+      if (vec_skip) {
+        for (int x0 = 4 * glue_lane(lg_skip); x0 < W; x0 += 4 << lg_skip) {
+          const float4 v = *reinterpret_cast<const float4*>(src + x0);
+          pad_row_store4(mid, x0, W, v);
+          if (top) pad_row_store4(top, x0, W, v);
+          if (bot) pad_row_store4(bot, x0, W, v);
+        }
+      } else {
+        for (int x = glue_lane(lg_skip); x < W; x += 1 << lg_skip) {
+          const float v = src[x];
+          pad_row_store1(mid, x, W, v);
+          if (top) pad_row_store1(top, x, W, v);
+          if (bot) pad_row_store1(bot, x, W, v);
+        }
+      }
+    }
+  }
+}
+
+// grad_z = g * ELU'(y), y = ELU(z + bias) recomputed, g = upcat_pad_bwd_kernel's 2x2 sum; grad_skip as there.  A lane of
+// the 16-byte form owns four low-resolution columns: the eight padded columns 2 j0 + 1 .. 2 j0 + 8 of a padded row are
+// two 16-byte loads (one lane fetches the pair 2j + 1, 2j + 2 together).  part[c][n * gridDim.x + blockIdx.x] = the
+// block's sum of grad_z in double.
+__global__ __launch_bounds__(RW * RR) void upcat_pad_act_bwd_kernel(const float* __restrict__ gout, const float* __restrict__ z,
+                                                                    const float* __restrict__ bias, float* __restrict__ gz,
+                                                                    float* __restrict__ gskip, double* __restrict__ part,
+                                                                    int N, int C1, int C2, int h, int w, int vec_z,
+                                                                    int vec_skip, int lg_z, int lg_skip) {
+  __shared__ double sh[RR];
+  const int H = 2 * h, W = 2 * w, PH = H + 2, PW = W + 2;
+  const int pl = blockIdx.y, n = pl / (C1 + C2), c = pl - n * (C1 + C2);
+  const float* g = gout + (size_t)pl * PH * PW;
+  if (c < C1) {
+    const int i = glue_row(lg_z);
+    double acc = 0.0;
+    if (i < h) {
+      const float b = bias[c];
+      const size_t base = (((size_t)n * C1 + c) * h + i) * w;
+      if (vec_z) {
+        for (int j0 = 4 * glue_lane(lg_z); j0 < w; j0 += 4 << lg_z) {
+          float a0[8], a1[8];
+          pad1_adjoint_run<8>(g, 2 * i, 2 * j0, H, W, a0);
+          pad1_adjoint_run<8>(g, 2 * i + 1, 2 * j0, H, W, a1);
+          float4 y = *reinterpret_cast<const float4*>(z + base + j0);
+          y.x = elu1(y.x + b); y.y = elu1(y.y + b); y.z = elu1(y.z + b); y.w = elu1(y.w + b);
+          float4 r;
+          r.x = elu1_grad((a0[0] + a0[1]) + (a1[0] + a1[1]), y.x);
+          r.y = elu1_grad((a0[2] + a0[3]) + (a1[2] + a1[3]), y.y);
+          r.z = elu1_grad((a0[4] + a0[5]) + (a1[4] + a1[5]), y.z);
+          r.w = elu1_grad((a0[6] + a0[7]) + (a1[6] + a1[7]), y.w);
+          *reinterpret_cast<float4*>(gz + base + j0) = r;
+          acc += (double)((r.x + r.y) + (r.z + r.w));
+        }
+      } else {
+        for (int j = glue_lane(lg_z); j < w; j += 1 << lg_z) {
+          const float gg = (pad1_adjoint(g, 2 * i, 2 * j, H, W) + pad1_adjoint(g, 2 * i, 2 * j + 1, H, W)) +
+                           (pad1_adjoint(g, 2 * i + 1, 2 * j, H, W) + pad1_adjoint(g, 2 * i + 1, 2 * j + 1, H, W));
+          const float r = elu1_grad(gg, elu1(z[base + j] + b));
+          gz[base + j] = r;
+          acc += (double)r;
+        }
+      }
+    }
+    const double t = block_sum_rows(acc, sh);
+    if (threadIdx.x == 0 && threadIdx.y == 0) part[((size_t)c * N + n) * gridDim.x + blockIdx.x] = t;
+  } else {
+    for (int y = glue_row(lg_skip); y < H; y += (gridDim.x * RR) << (6 - lg_skip)) {
+      float* dst = gskip + (((size_t)n * C2 + (c - C1)) * H + y) * W;
+      if (vec_skip) {
+        for (int x0 = 4 * glue_lane(lg_skip); x0 < W; x0 += 4 << lg_skip) {
+          float a[4];
+          pad1_adjoint_run<4>(g, y, x0, H, W, a);
+          *reinterpret_cast<float4*>(dst + x0) = make_float4(a[0], a[1], a[2], a[3]);
+        }
+      } else {
+        for (int xx = glue_lane(lg_skip); xx < W; xx += 1 << lg_skip) dst[xx] = pad1_adjoint(g, y, xx, H, W);
+      }
+    }
+  }
+}
+
+// y <- ELU(y + bias) in place and yp = ReflectionPad2d(1)(y): image row r is padded row r + 1, and also padded row 0
+// (r = 1) and H + 1 (r = H - 2).
+__global__ __launch_bounds__(RW * RR) void bias_elu_pad_fwd_kernel(float* __restrict__ y, const float* __restrict__ bias,
+                                                                   float* __restrict__ yp, int C, int H, int W, int vec, int lg) {
+  const int PH = H + 2, PW = W + 2;
+  const int r = glue_row(lg);
+  if (r >= H) return;
+  const size_t pl = blockIdx.y;
+  const float b = bias[(int)(pl % C)];
+  float* row = y + (pl * H + r) * W;
+  float* dst = yp + pl * PH * PW;
+  float* mid = dst + (size_t)(r + 1) * PW;
+  float* top = r == 1 ? dst : nullptr;
+  float* bot = r == H - 2 ? dst + (size_t)(H + 1) * PW : nullptr;
+  if (vec) {
+    for (int x0 = 4 * glue_lane(lg); x0 < W; x0 += 4 << lg) {
+      float4 v = *reinterpret_cast<float4*>(row + x0);
+      v.x = elu1(v.x + b); v.y = elu1(v.y + b); v.z = elu1(v.z + b); v.w = elu1(v.w + b);
+      *reinterpret_cast<float4*>(row + x0) = v;
+      pad_row_store4(mid, x0, W, v);
+      if (top) pad_row_store4(top, x0, W, v);
+      if (bot) pad_row_store4(bot, x0, W, v);
+    }
+  } else {
+    for (int x = glue_lane(lg); x < W; x += 1 << lg) {
+      const float v = elu1(row[x] + b);
+      row[x] = v;
+      pad_row_store1(mid, x, W, v);
+      if (top) pad_row_store1(top, x, W, v);
+      if (bot) pad_row_store1(bot, x, W, v);
+    }
+  }
+}
+
+// grad_z = (pad1_adjoint(grad_yp) + grad_y) * ELU'(y); either gradient may be NULL.  part as in upcat_pad_act_bwd_kernel.
+__global__ __launch_bounds__(RW * RR) void bias_elu_pad_bwd_kernel(const float* __restrict__ gyp, const float* __restrict__ gy,
+                                                                   const float* __restrict__ y, float* __restrict__ gz,
+                                                                   double* __restrict__ part, int N, int C, int H, int W,
+                                                                   int vec, int lg) {
+  __shared__ double sh[RR];
+  const int PH = H + 2, PW = W + 2;
+  const int r = glue_row(lg);
+  const int pl = blockIdx.y, n = pl / C, c = pl - n * C;
+  const float* g = gyp ? gyp + (size_t)pl * PH * PW : nullptr;
+  double acc = 0.0;
+  if (r < H) {
+    const size_t base = ((size_t)pl * H + r) * W;
+    if (vec) {
+      for (int x0 = 4 * glue_lane(lg); x0 < W; x0 += 4 << lg) {
+        float a[4];
+        if (g) {
+          pad1_adjoint_run<4>(g, r, x0, H, W, a);
+          if (gy) {
+            const float4 u = *reinterpret_cast<const float4*>(gy + base + x0);
+            a[0] += u.x; a[1] += u.y; a[2] += u.z; a[3] += u.w;
+          }
+        } else {
+          const float4 u = *reinterpret_cast<const float4*>(gy + base + x0);
+          a[0] = u.x; a[1] = u.y; a[2] = u.z; a[3] = u.w;
+        }
+        const float4 o = *reinterpret_cast<const float4*>(y + base + x0);
+        float4 q;
+        q.x = elu1_grad(a[0], o.x); q.y = elu1_grad(a[1], o.y); q.z = elu1_grad(a[2], o.z); q.w = elu1_grad(a[3], o.w);
+        *reinterpret_cast<float4*>(gz + base + x0) = q;
+        acc += (double)((q.x + q.y) + (q.z + q.w));
+      }
+    } else {
+      for (int x = glue_lane(lg); x < W; x += 1 << lg) {
+        float a;
+        if (g) {
+          a = pad1_adjoint(g, r, x, H, W);
+          if (gy) a += gy[base + x];
+        } else {
+          a = gy[base + x];
+        }
+        const float q = elu1_grad(a, y[base + x]);
+        gz[base + x] = q;
+        acc += (double)q;
+      }
+    }
+  }
+  const double t = block_sum_rows(acc, sh);
+  if (threadIdx.x == 0 && threadIdx.y == 0) part[((size_t)c * N + n) * gridDim.x + blockIdx.x] = t;
+}
+
+// grad_bias[c] = sum of the channel's `count` block partials: one wave per channel, lane l adds partials l, l + 64, ...
+// in order, then the lanes are folded - a fixed order for a given shape.
+__global__ __launch_bounds__(64) void bias_grad_final_wave_kernel(const double* __restrict__ part, float* __restrict__ gbias,
+                                                                  int count) {
+  const double* p = part + (size_t)blockIdx.x * count;
+  double s = 0.0;
+  for (int k = threadIdx.x; k < count; k += 64) s += p[k];
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+  if (threadIdx.x == 0) gbias[blockIdx.x] = (float)s;
+}
+
 // MaxPool2d(kernel 3, stride 2, padding 1): ATen's scan order and tie / NaN rule (first maximum in
 // row-major window order; a NaN replaces the running maximum).  `code` = window position 0..8.
 __global__ __launch_bounds__(RW * RR) void maxpool3s2_fwd_kernel(const float* __restrict__ in,
@@ -1585,6 +1893,74 @@ int bbd_bias_elu_bwd(const float* y, const float* grad_y, float* grad_x, float* 
   hipLaunchKernelGGL(bias_elu_bwd_kernel, dim3((unsigned)split, (unsigned)C), dim3(NT), 0, st, y, grad_y, grad_x, scratch, N, C,
                      HW, split);
   hipLaunchKernelGGL(bias_grad_final_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, st, scratch, grad_bias, C, split);
+  return status();
+}
+
+namespace {
+// may this tensor be read or written in float4 steps?  (NULL: it is not touched)
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// glue_row / glue_lane: log2 of the lanes along a row whose lanes have `items` things to do in all, and the workgroups
+// that then cover `rows` rows
+int glue_lanes_log2(int items) {
+  int lg = 0;
+  while (lg < 6 && (1 << lg) < items) ++lg;
+  return lg;
+}
+int glue_blocks(int rows, int lg) {
+  const int per = RR << (6 - lg);
+  return (rows + per - 1) / per;
+}
+}  // namespace
+
+int bbd_upcat_pad_act_fwd(const float* z, const float* bias, const float* skip, float* out, int N, int C1, int C2, int h, int w,
+                          void* stream) {
+  if (!z || !bias || !out || N <= 0 || C1 <= 0 || C2 < 0 || (C2 > 0 && !skip) || h < 1 || w < 1) return BBD_E_BADARG;
+  if ((long)N * (C1 + C2) > 65535 || (2L * h + 2) * (2L * w + 2) > 2147483647L) return BBD_E_BADARG;
+  const int vec_z = (w % 4 == 0) && aligned16(z), vec_skip = (w % 2 == 0) && aligned16(skip);
+  const int lg_z = glue_lanes_log2(vec_z ? w / 4 : w), lg_skip = glue_lanes_log2(vec_skip ? w / 2 : 2 * w);
+  hipLaunchKernelGGL(upcat_pad_act_fwd_kernel, dim3((unsigned)glue_blocks(h, lg_z), (unsigned)(N * (C1 + C2))), dim3(RW, RR), 0,
+                     static_cast<hipStream_t>(stream), z, bias, skip, out, C1, C2, h, w, vec_z, vec_skip, lg_z, lg_skip);
+  return status();
+}
+
+int bbd_upcat_pad_act_bwd(const float* grad_out, const float* z, const float* bias, float* grad_z, float* grad_skip,
+                          float* grad_bias, double* scratch, int scratch_doubles, int N, int C1, int C2, int h, int w,
+                          void* stream) {
+  if (!grad_out || !z || !bias || !grad_z || !grad_bias || !scratch || N <= 0 || C1 <= 0 || C2 < 0 || (C2 > 0 && !grad_skip) ||
+      h < 1 || w < 1)
+    return BBD_E_BADARG;
+  if ((long)N * (C1 + C2) > 65535 || (2L * h + 2) * (2L * w + 2) > 2147483647L) return BBD_E_BADARG;
+  if ((long)C1 * N * ((h + RR - 1) / RR) > scratch_doubles) return BBD_E_BADARG;
+  const int vec_z = (w % 4 == 0) && aligned16(z) && aligned16(grad_z), vec_skip = (w % 2 == 0) && aligned16(grad_skip);
+  const int lg_z = glue_lanes_log2(vec_z ? w / 4 : w), lg_skip = glue_lanes_log2(vec_skip ? w / 2 : 2 * w);
+  const int gx = glue_blocks(h, lg_z);          // <= ceil(h / BBD_GLUE_ROWS), the partials the caller made room for
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(upcat_pad_act_bwd_kernel, dim3((unsigned)gx, (unsigned)(N * (C1 + C2))), dim3(RW, RR), 0, st, grad_out, z,
+                     bias, grad_z, grad_skip, scratch, N, C1, C2, h, w, vec_z, vec_skip, lg_z, lg_skip);
+  hipLaunchKernelGGL(bias_grad_final_wave_kernel, dim3((unsigned)C1), dim3(64), 0, st, scratch, grad_bias, N * gx);
+  return status();
+}
+
+int bbd_bias_elu_pad_fwd(float* y, const float* bias, float* yp, int N, int C, int H, int W, void* stream) {
+  if (!y || !bias || !yp || N <= 0 || C <= 0 || (long)N * C > 65535 || H < 2 || W < 2) return BBD_E_BADARG;
+  const int vec = (W % 4 == 0) && aligned16(y), lg = glue_lanes_log2(vec ? W / 4 : W);
+  hipLaunchKernelGGL(bias_elu_pad_fwd_kernel, dim3((unsigned)glue_blocks(H, lg), (unsigned)(N * C)), dim3(RW, RR), 0,
+                     static_cast<hipStream_t>(stream), y, bias, yp, C, H, W, vec, lg);
+  return status();
+}
+
+int bbd_bias_elu_pad_bwd(const float* grad_yp, const float* grad_y, const float* y, float* grad_z, float* grad_bias,
+                         double* scratch, int scratch_doubles, int N, int C, int H, int W, void* stream) {
+  if ((!grad_yp && !grad_y) || !y || !grad_z || !grad_bias || !scratch || N <= 0 || C <= 0 || (long)N * C > 65535 || H < 2 ||
+      W < 2)
+    return BBD_E_BADARG;
+  if ((long)C * N * ((H + RR - 1) / RR) > scratch_doubles) return BBD_E_BADARG;
+  const int vec = (W % 4 == 0) && aligned16(y) && aligned16(grad_z) && aligned16(grad_y);
+  const int lg = glue_lanes_log2(vec ? W / 4 : W), gx = glue_blocks(H, lg);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(bias_elu_pad_bwd_kernel, dim3((unsigned)gx, (unsigned)(N * C)), dim3(RW, RR), 0, st, grad_yp, grad_y, y,
+                     grad_z, scratch, N, C, H, W, vec, lg);
+  hipLaunchKernelGGL(bias_grad_final_wave_kernel, dim3((unsigned)C), dim3(64), 0, st, scratch, grad_bias, N * gx);
   return status();
 }
 

@@ -121,11 +121,19 @@ class ConvBlock(nn.Module):
         conv = self.conv.conv
         out_hw = (xp.shape[2] - 2) * (xp.shape[3] - 2)
         if xp.is_cuda and xp.dtype == torch.float32 and ops.FUSED_NN and conv.bias is not None and out_hw % 4 == 0:
-            y = torch.nn.functional.conv2d(xp, conv.weight, None)
-            if y.is_contiguous():        # channels-last inputs / NHWC policies can hand back a strided result
-                return ops.bias_elu_(y, conv.bias)
-            return self.nonlin(y + conv.bias.view(1, -1, 1, 1))
+            return self.bias_act_(self.conv_raw(xp))
         return self.nonlin(conv(xp))
+
+    def conv_raw(self, xp):
+        """The bias-free convolution of the padded input: what `bias_act_` and the decoder's fused glue start from."""
+        return torch.nn.functional.conv2d(xp, self.conv.conv.weight, None)
+
+    def bias_act_(self, y):
+        """bias + ELU on `conv_raw`'s result (H * W a multiple of 4), in place where the HIP pass takes it."""
+        conv = self.conv.conv
+        if y.is_contiguous():        # channels-last inputs / NHWC policies can hand back a strided result
+            return ops.bias_elu_(y, conv.bias)
+        return self.nonlin(y + conv.bias.view(1, -1, 1, 1))
 
 
 def upsample(x):

@@ -42,13 +42,36 @@ class DepthDecoder(nn.Module):
     def _stage(self, *key):
         return self.decoder[self._slot[key]]
 
+    def _glue_level(self, level, x):
+        """Do both ConvBlocks of `level` start from a bias-free convolution of input `x`, so that bias + ELU can move
+        into the glue passes (BBD_FUSED_DECODER_GLUE=0: never)?"""
+        return (ops.FUSED_DECODER_GLUE and self._stage("upconv", level, 0)._fused(x)
+                and self._stage("upconv", level, 1).conv.conv.bias is not None)
+
     def forward(self, input_features):
         self.outputs = {}
         x = input_features[-1]
+        xp = None       # x with its reflection border, where the level above wrote both in one pass (ops.bias_elu_pad)
         for level in reversed(range(5)):
-            x = self._stage("upconv", level, 0)(x)
+            first, second = self._stage("upconv", level, 0), self._stage("upconv", level, 1)
             skip = input_features[level - 1] if (self.use_skips and level > 0) else None
-            if ops.upcat_pad_supported(x, skip):
+            glued = False
+            if self._glue_level(level, x):
+                # the blocks' bias + ELU ride on the glue passes: conv -> upcat_pad_act -> conv -> bias_elu_pad
+                z = first.conv_raw(xp if xp is not None else first.conv.pad(x))
+                glued = ops.upcat_pad_act_supported(z, first.conv.conv.bias, skip)
+                if not glued:
+                    x = first.bias_act_(z)              # what first(x) does
+            else:
+                x = first(x)
+            xp = None
+            if glued:
+                z = second.conv_raw(ops.upcat_pad_act(z, first.conv.conv.bias, skip))
+                if level > 0 and self._glue_level(level - 1, z) and ops.bias_elu_pad_supported(z, second.conv.conv.bias):
+                    x, xp = ops.bias_elu_pad(z, second.conv.conv.bias)
+                else:
+                    x = second.bias_act_(z)             # level 0: nothing pads its output
+            elif ops.upcat_pad_supported(x, skip):
                 # nearest x2 + skip concatenation + the next block's reflection border in ONE HIP pass
                 x = self._stage("upconv", level, 1).forward_padded(ops.upcat_pad(x, skip))
             else:

@@ -1551,6 +1551,118 @@ def bias_elu_(conv_out, bias, backend=None):
     return _BiasELU.apply(conv_out, bias, backend or default_backend())
 
 
+# ---------------------------------------------------------------------------- decoder glue with bias + ELU inside
+# 0: upcat_pad / bias_elu_ / reflect_pad1 one after the other, as before (A/B runs)
+FUSED_DECODER_GLUE = os.environ.get("BBD_FUSED_DECODER_GLUE", "1") != "0"
+
+
+def _glue_scratch(channels, N, rows, device):
+    """the per-workgroup partials of a glue backward's bias gradient (include/bbd_hip.h, BBD_GLUE_ROWS)"""
+    n = channels * N * (-(-rows // _lib.GLUE_ROWS))
+    return torch.empty(n, device=device, dtype=torch.float64), n
+
+
+def _glue_tensor(t):
+    return t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+
+
+def upcat_pad_act_supported(z, bias, skip):
+    """Does `bbd_upcat_pad_act_*` take the convolution output `z` [N,C1,h,w] with `skip` [N,C2,2h,2w] or None?"""
+    if z.dim() != 4 or bias is None or not (_glue_tensor(z) and _glue_tensor(bias)):
+        return False
+    N, C1, h, w = z.shape
+    if skip is not None and not (_glue_tensor(skip) and skip.shape == (N, skip.shape[1], 2 * h, 2 * w)):
+        return False
+    return h >= 1 and w >= 1 and 1 <= N * (C1 + (skip.shape[1] if skip is not None else 0)) <= 65535
+
+
+def bias_elu_pad_supported(z, bias):
+    """Does `bbd_bias_elu_pad_*` take the convolution output `z` [N,C,H,W]?"""
+    if z.dim() != 4 or bias is None or not (_glue_tensor(z) and _glue_tensor(bias)):
+        return False
+    N, C, H, W = z.shape
+    return H >= 2 and W >= 2 and 1 <= N * C <= 65535
+
+
+class _UpCatPadAct(torch.autograd.Function):
+    """`upcat_pad(bias_elu_(z, bias), skip)` in one pass each way; `z` stays as the convolution wrote it and is what the
+    backward reads (csrc/bbd_nn.hip, bbd_upcat_pad_act_*)."""
+
+    @staticmethod
+    def forward(ctx, z, bias, skip, backend):
+        backend._check(z, bias, skip)
+        z, bias = z.contiguous(), bias.contiguous()
+        N, C1, h, w = z.shape
+        C2 = 0
+        if skip is not None:
+            skip = skip.contiguous()
+            C2 = skip.shape[1]
+            assert skip.shape == (N, C2, 2 * h, 2 * w)
+        out = torch.empty(N, C1 + C2, 2 * h + 2, 2 * w + 2, device=z.device, dtype=torch.float32)
+        backend.run("bbd_upcat_pad_act_fwd", z, ptr(z), ptr(bias), ptr(skip), ptr(out), N, C1, C2, h, w)
+        ctx.save_for_backward(z, bias)
+        ctx.meta = (C2, backend)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        z, bias = ctx.saved_tensors
+        C2, backend = ctx.meta
+        N, C1, h, w = z.shape
+        gout = gout.contiguous()
+        gz = torch.empty_like(z)
+        gs = torch.empty(N, C2, 2 * h, 2 * w, device=z.device, dtype=torch.float32) if C2 else None
+        gb = torch.empty(C1, device=z.device, dtype=torch.float32)
+        scratch, n = _glue_scratch(C1, N, h, z.device)
+        backend.run("bbd_upcat_pad_act_bwd", gout, ptr(gout), ptr(z), ptr(bias), ptr(gz), ptr(gs), ptr(gb), ptr(scratch), n,
+                    N, C1, C2, h, w)
+        return gz, gb, gs, None
+
+
+def upcat_pad_act(z, bias, skip=None, backend=None):
+    """ReflectionPad2d(1)(cat(nearest_x2(ELU(z + bias)), skip)): a ConvBlock's bias + ELU inside `upcat_pad`."""
+    return _UpCatPadAct.apply(z, bias, skip, backend or default_backend())
+
+
+class _BiasEluPad(torch.autograd.Function):
+    """`y = bias_elu_(z, bias); yp = reflect_pad1(y)` in one pass each way -> (y, yp); y is z, written in place.  Backward
+    takes the gradients of both outputs (either may be missing) in one pass (csrc/bbd_nn.hip, bbd_bias_elu_pad_*)."""
+
+    @staticmethod
+    def forward(ctx, z, bias, backend):
+        backend._check(z, bias)
+        assert z.is_contiguous()
+        bias = bias.contiguous()
+        N, C, H, W = z.shape
+        yp = torch.empty(N, C, H + 2, W + 2, device=z.device, dtype=torch.float32)
+        backend.run("bbd_bias_elu_pad_fwd", z, ptr(z), ptr(bias), ptr(yp), N, C, H, W)
+        ctx.mark_dirty(z)
+        ctx.save_for_backward(z)
+        ctx.backend = backend
+        ctx.set_materialize_grads(False)
+        return z, yp
+
+    @staticmethod
+    def backward(ctx, gy, gyp):
+        if gy is None and gyp is None:
+            return None, None, None
+        (y,) = ctx.saved_tensors
+        backend = ctx.backend
+        N, C, H, W = y.shape
+        gy = gy.contiguous() if gy is not None else None
+        gyp = gyp.contiguous() if gyp is not None else None
+        gz = torch.empty_like(y)
+        gb = torch.empty(C, device=y.device, dtype=torch.float32)
+        scratch, n = _glue_scratch(C, N, H, y.device)
+        backend.run("bbd_bias_elu_pad_bwd", y, ptr(gyp), ptr(gy), ptr(y), ptr(gz), ptr(gb), ptr(scratch), n, N, C, H, W)
+        return gz, gb, None
+
+
+def bias_elu_pad(conv_out, bias, backend=None):
+    """(y, yp) = (ELU(conv_out + bias) in place, ReflectionPad2d(1)(y)): a ConvBlock's tail and the next one's border."""
+    return _BiasEluPad.apply(conv_out, bias, backend or default_backend())
+
+
 # ---------------------------------------------------------------------------- disparity head Conv3x3(C -> 1)
 class _DispConv(torch.autograd.Function):
     @staticmethod

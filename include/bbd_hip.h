@@ -54,8 +54,9 @@ extern "C" {
  * 18 = bbd_ground_scale (metric scale of a prediction from the camera's height above the ground);
  * 19 = bbd_disp_head_fwd / _bwd (the disparity head with its sigmoid inside);
  * 20 = bbd_depth_consistency (depth-pose geometric consistency: a score and a filter for the scene map);
- * 21 = bbd_stem_* (the encoder stem: BatchNorm + ReLU + max-pool in one pass each way). */
-#define BBD_ABI_VERSION 21
+ * 21 = bbd_stem_* (the encoder stem: BatchNorm + ReLU + max-pool in one pass each way);
+ * 22 = bbd_upcat_pad_act_* / bbd_bias_elu_pad_* (the depth decoder's bias + ELU inside its pad / up-sample passes). */
+#define BBD_ABI_VERSION 22
 
 /* Source frames live in separate tensors, one per frame id (inputs[("color", f, 0)],
  * trainer.py:428).  A "slot" indexes a host array of their base pointers. */
@@ -988,6 +989,32 @@ int bbd_bias_elu_scratch_doubles(int N, int C, int HW);
 int bbd_bias_elu_fwd(float* y, const float* bias, int N, int C, int HW, void* stream);
 int bbd_bias_elu_bwd(const float* y, const float* grad_y, float* grad_x, float* grad_bias, double* scratch, int N, int C,
                      int HW, void* stream);
+
+/* The same glue with the ConvBlock's bias + ELU inside (DepthDecoder levels 4..1), fp32 NCHW.  Values are
+ * those of the entry points above applied one after the other, bit for bit; the bias gradients add the same numbers in
+ * another (fixed) order.
+ *   bbd_upcat_pad_act_fwd : out [N, C1+C2, 2h+2, 2w+2] = ReflectionPad2d(1)(cat(nearest_x2(ELU(z + bias)), skip)) from the
+ *                           bias-free convolution output z [N,C1,h,w], which is left as it is (skip may be NULL, C2 = 0)
+ *   bbd_upcat_pad_act_bwd : grad_z = g * ELU'(y) with y recomputed from z + bias and g the gradient bbd_upcat_pad1_bwd
+ *                           hands to x; grad_skip as there; grad_bias [C1] = sum grad_z
+ *   bbd_bias_elu_pad_fwd  : y [N,C,H,W] <- ELU(y + bias[c]) in place and yp [N,C,H+2,W+2] = ReflectionPad2d(1)(y)
+ *   bbd_bias_elu_pad_bwd  : grad_z = (the gradient bbd_reflect_pad1_bwd makes of grad_yp + grad_y) * ELU'(y) from the
+ *                           saved output y; grad_yp or grad_y may be NULL, not both; grad_bias [C] = sum grad_z
+ * Both backwards are one pass plus a one-wave-per-channel sum of per-workgroup float64 partials (no atomics): scratch
+ * holds at least channels * N * ceil(rows / BBD_GLUE_ROWS) doubles, rows = h resp. H, channels = C1 resp. C, and
+ * scratch_doubles says how many it has.  No allocation, no host synchronisation, every element of every output is
+ * written.  N * (C1 + C2) resp. N * C above 65535, H or W below 2, h or w below 1, a padded plane of 2^31 elements or more, a missing pointer or
+ * a scratch that is too small return BBD_E_BADARG and launch nothing.  Rows of whole float4s in 16-byte aligned tensors move 16 bytes per
+ * lane, everything else one float. */
+#define BBD_GLUE_ROWS 4
+int bbd_upcat_pad_act_fwd(const float* z, const float* bias, const float* skip, float* out, int N, int C1, int C2, int h, int w,
+                          void* stream);
+int bbd_upcat_pad_act_bwd(const float* grad_out, const float* z, const float* bias, float* grad_z, float* grad_skip,
+                          float* grad_bias, double* scratch, int scratch_doubles, int N, int C1, int C2, int h, int w,
+                          void* stream);
+int bbd_bias_elu_pad_fwd(float* y, const float* bias, float* yp, int N, int C, int H, int W, void* stream);
+int bbd_bias_elu_pad_bwd(const float* grad_yp, const float* grad_y, const float* y, float* grad_z, float* grad_bias,
+                         double* scratch, int scratch_doubles, int N, int C, int H, int W, void* stream);
 
 /* ---- MonoViT encoder (BASELINE configs[4]): depth-wise convolution on token-layout activations ----------
  * The position encodings of the reference's MPViT (networksvit/mpvit.py:240-330: ConvPosEnc, ConvRelPosEnc)
