@@ -40,6 +40,7 @@ SRCS = _here("""
     bbd_map.hip
     bbd_view.hip
     bbd_consist.hip
+    bbd_uncert.hip
 """)
 OUT = os.path.join(HERE, "libbbd_hip.so")
 # every header of this directory: one that is forgotten here would leave a stale library behind an edit

@@ -322,7 +322,21 @@ def evaluate(opt, dataloader=None, gt_depths=None, models=None, batch_size=16, g
     returned ratios are the recovered scales; an image without ground has a NaN scale, is named in a warning and left
     out of the mean.  Refused with `eval_stereo`, `disable_median_scaling` and the SYNS split.
 
+    Uncertainty (KITTI splits only), each field read with a default:
+      `uncertainty`        "none" | "post": under "post" every batch runs with its flipped copy (`post_process` is
+                           implied), the blended disparity is scored and |d - flip(d')| - the "Post" uncertainty of Poggi
+                           et al. - comes out of the same `ops.post_process_uncert` launch.  Every batch then gets one
+                           `ops.sparsification` call right after `depth_metrics`; its rows are read back with the metrics
+                           rows, once.  After the metrics table a table of AUSE and AURG for abs_rel, rmse and a1 is
+                           printed: the mean over the images that have a scored pixel (the others are named).
+      `ext_uncert_to_eval` a float [N,h,w] .npy with the uncertainties of the disparities of `ext_disp_to_eval`.
+      `save_pred_uncerts`  writes `uncerts_<eval_split>_split.npy` next to `disps_<eval_split>_split.npy`.
+      `sparsification_intervals` (50) and `save_sparsification` (a .json: the mean curves and the six numbers).
+    With an uncertainty, (mean_errors, ratios, scores) is returned, `scores` being the dict `save_sparsification`
+    writes.  Refused with the SYNS split, `no_eval` and `scale_recovery ground`.
+
     `backend` and `device` are for tests (the host ports); by default the HIP backend and `cuda:<opt.cuda>`."""
+    uncert = _uncert_options(opt)                                        # raises before anything is touched
     from . import tuning
     tuning.use_shipped_db()      # (no Trainer is built here: the tuned MIOpen database is wired explicitly)
     import os
@@ -342,10 +356,12 @@ def evaluate(opt, dataloader=None, gt_depths=None, models=None, batch_size=16, g
         if syns:
             return _evaluate_syns(opt, source, save_path, no_eval, gt_depths, gt_edges, inv_K, split_dir, device,
                                   backend, clouds)
-        return _evaluate_kitti(opt, source, save_path, no_eval, gt_depths, split_dir, device, backend, clouds)
+        return _evaluate_kitti(opt, source, save_path, no_eval, gt_depths, split_dir, device, backend, clouds, uncert)
 
     if ext is not None:
-        return score(_ExternalDisps(ext, batch_size, device), None)
+        return score(_ExternalDisps(ext, batch_size, device, uncert["ext"] if uncert else None), None)
+    if uncert is not None and uncert["save"]:
+        uncert["save_path"] = _disps_path(opt).replace("disps_", "uncerts_")               # raises before any prediction
     save_path = _disps_path(opt) if getattr(opt, "save_pred_disps", False) else None      # raises before any prediction
     if models is None:
         folder = os.path.expanduser(opt.load_weights_folder)
@@ -378,17 +394,21 @@ def evaluate(opt, dataloader=None, gt_depths=None, models=None, batch_size=16, g
                                           naive_mix=True)
         dataloader = datasets.DeviceLoader(ds, batch_size, datasets.DeviceCollate(height, width, [0], device),
                                            shuffle=False, drop_last=False, num_workers=getattr(opt, "num_workers", 8))
-    return score(_PredictedDisps(opt, dataloader, encoder, decoder, bool(getattr(opt, "post_process", False))), save_path)
+    if uncert is not None:
+        print("-> uncertainty post: every batch runs with its flipped copy (post_process is implied)")
+    post_process = bool(getattr(opt, "post_process", False)) or uncert is not None
+    return score(_PredictedDisps(opt, dataloader, encoder, decoder, post_process, uncert is not None, backend), save_path)
 
 
 class _PredictedDisps:
     """The disparities that are scored, batch by batch on the device: `disp_to_depth` of the networks' output and, with
-    `post_process`, the flip blend of the batch and its mirrored copy ([n,h,w] then, [n,1,h,w] otherwise)."""
+    `post_process`, the flip blend of the batch and its mirrored copy ([n,h,w] then, [n,1,h,w] otherwise).  With `uncert`
+    every item is the pair (blended disparities, their uncertainty), both from one `ops.post_process_uncert` launch."""
     count = None                 # known only after the loader has run dry
 
-    def __init__(self, opt, dataloader, encoder, decoder, post_process):
+    def __init__(self, opt, dataloader, encoder, decoder, post_process, uncert=False, backend=None):
         self.opt, self.dataloader, self.encoder, self.decoder = opt, dataloader, encoder, decoder
-        self.post_process = post_process
+        self.post_process, self.uncert, self.backend = post_process, uncert, backend
 
     def __iter__(self):
         from .layers import disp_to_depth
@@ -398,25 +418,47 @@ class _PredictedDisps:
                 x = torch.cat((x, torch.flip(x, [3])), 0)
             out = self.decoder(self.encoder(x))
             pred_disp, _ = disp_to_depth(out[("disp", 0)], self.opt.min_depth, self.opt.max_depth)
-            yield ops.post_process_disp(pred_disp) if self.post_process else pred_disp
+            if self.uncert:
+                yield ops.post_process_uncert(pred_disp, backend=self.backend)
+            else:
+                yield ops.post_process_disp(pred_disp, backend=self.backend) if self.post_process else pred_disp
 
 
 class _ExternalDisps:
     """Disparities of a saved file (`--ext_disp_to_eval`): a numeric [N,h,w] array, cast to float32 and uploaded in
-    batches of `batch_size`."""
+    batches of `batch_size`.  With `uncert_path` (`--ext_uncert_to_eval`: a file of the same shape, checked the same way)
+    every item is the pair (disparities, their uncertainties)."""
 
-    def __init__(self, path, batch_size, device):
+    def __init__(self, path, batch_size, device, uncert_path=None):
+        arr = self._load(path, "ext_disp_to_eval")
+        self.uncert = None
+        if uncert_path is not None:
+            self.uncert = self._load(uncert_path, "ext_uncert_to_eval")
+            if self.uncert.shape != arr.shape:
+                raise ValueError("ext_uncert_to_eval: %s holds %s, the disparities of %s are %s"
+                                 % (uncert_path, self.uncert.shape, path, arr.shape))
+        print("-> Loading predictions from {}".format(path))
+        if uncert_path is not None:
+            print("-> Loading uncertainties from {}".format(uncert_path))
+        self.arr, self.batch_size, self.device, self.count = arr, max(1, int(batch_size)), device, arr.shape[0]
+
+    @staticmethod
+    def _load(path, what):
         arr = np.load(path)
         if not isinstance(arr, np.ndarray) or arr.ndim != 3 or arr.dtype.kind not in "fiu" or 0 in arr.shape:
-            raise ValueError("ext_disp_to_eval: %s must hold a numeric [N,h,w] array, got %s"
-                             % (path, "%s %s" % (arr.dtype, arr.shape) if isinstance(arr, np.ndarray) else type(arr)))
-        print("-> Loading predictions from {}".format(path))
-        self.arr, self.batch_size, self.device, self.count = arr, max(1, int(batch_size)), device, arr.shape[0]
+            raise ValueError("%s: %s must hold a numeric [N,h,w] array, got %s"
+                             % (what, path, "%s %s" % (arr.dtype, arr.shape) if isinstance(arr, np.ndarray) else type(arr)))
+        return arr
+
+    def _chunk(self, arr, first):
+        return torch.from_numpy(np.ascontiguousarray(arr[first:first + self.batch_size], dtype=np.float32)).to(self.device)
 
     def __iter__(self):
         for first in range(0, self.count, self.batch_size):
-            chunk = np.ascontiguousarray(self.arr[first:first + self.batch_size], dtype=np.float32)
-            yield torch.from_numpy(chunk).to(self.device)
+            if self.uncert is None:
+                yield self._chunk(self.arr, first)
+            else:
+                yield self._chunk(self.arr, first), self._chunk(self.uncert, first)
 
 
 def _disps_path(opt):
@@ -538,8 +580,63 @@ def _ground_summary(rows, ground_rows):
     return mean_errors, ratios
 
 
-def _evaluate_kitti(opt, source, save_path, no_eval, gt_depths, split_dir, device, backend=None, clouds=None):
-    """The KITTI splits: every batch of `source` is scored by one `bbd_depth_metrics` launch while it is in HBM."""
+UNCERT_METRICS = ("abs_rel", "rmse", "a1")
+
+
+def _uncert_options(opt):
+    """The uncertainty options of `opt` -> None (none asked for) or dict(ext, save, intervals, json); what they collide
+    with is refused (`options.uncertainty_conflict`)."""
+    from .options import uncertainty_conflict
+    conflict = uncertainty_conflict(opt)
+    if conflict:
+        raise ValueError(conflict)
+    ext = getattr(opt, "ext_uncert_to_eval", None)
+    if getattr(opt, "uncertainty", "none") != "post" and ext is None:
+        return None
+    return dict(ext=ext, save=bool(getattr(opt, "save_pred_uncerts", False)), save_path=None,
+                intervals=int(getattr(opt, "sparsification_intervals", 50)), json=getattr(opt, "save_sparsification", None))
+
+
+def sparsification_scores(spars, intervals):
+    """The scores of a split from the float64 rows [N, 8 + 6 (K + 1)] of `ops.sparsification`: the mean over the images
+    that have a scored pixel of AUSE, AURG and the six curves; `skipped` lists the others."""
+    K = int(intervals)
+    spars = np.asarray(spars, np.float64)
+    has = spars[:, 6] > 0
+    with np.errstate(invalid="ignore"):
+        mean = spars[has].mean(0) if has.any() else np.full(spars.shape[1], np.nan)
+    curves = mean[8:].reshape(2, 3, K + 1)
+    return dict(intervals=K, images=int(has.sum()), skipped=[int(i) for i in np.nonzero(~has)[0]],
+                fractions=[k / K for k in range(K + 1)],
+                ause={m: float(mean[j]) for j, m in enumerate(UNCERT_METRICS)},
+                aurg={m: float(mean[3 + j]) for j, m in enumerate(UNCERT_METRICS)},
+                curves={name: {m: curves[w, j].tolist() for j, m in enumerate(UNCERT_METRICS)}
+                        for w, name in enumerate(("sparse", "oracle"))})
+
+
+def _uncert_summary(spars, uncert):
+    """Prints the AUSE / AURG table of a split and writes `save_sparsification`; returns the scores."""
+    scores = sparsification_scores(spars, uncert["intervals"])
+    if scores["skipped"]:
+        print("   WARNING: no scored pixel in {:d} of {:d} images, left out of the uncertainty scores: {}".format(
+            len(scores["skipped"]), len(spars), ", ".join(str(i) for i in scores["skipped"])))
+    print("\n  Uncertainty, sparsification at {:d} fractions (AUSE: lower is better, AURG: higher is better)".format(
+        scores["intervals"]))
+    print("  " + "{:>8} | ".format("") + ("{:>8} | " * 3).format(*UNCERT_METRICS))
+    for name in ("ause", "aurg"):
+        values = [scores[name][m] for m in UNCERT_METRICS]
+        print("  " + "{:>8} | ".format(name.upper()) + ("{: 8.4f} | " * 3).format(*values))
+    if uncert["json"] is not None:
+        import json
+        with open(uncert["json"], "w") as f:
+            json.dump(scores, f, indent=1)
+        print("-> Saved the sparsification curves to ", uncert["json"])
+    return scores
+
+
+def _evaluate_kitti(opt, source, save_path, no_eval, gt_depths, split_dir, device, backend=None, clouds=None, uncert=None):
+    """The KITTI splits: every batch of `source` is scored by one `bbd_depth_metrics` launch while it is in HBM - and,
+    with `uncert`, its uncertainty maps by one `bbd_sparsification` launch right after."""
     import os
     if no_eval:
         return _predict_only(source, save_path)
@@ -564,8 +661,13 @@ def _evaluate_kitti(opt, source, save_path, no_eval, gt_depths, split_dir, devic
     if ground is not None:                                # the scale comes from the ground rows: nothing else scales
         median_scaling, scale = False, 1
     rows, ground_rows, kept, first = [], [], [], 0
+    spars, kept_uncerts = [], []
     with torch.no_grad():
         for pred_disp in source:
+            if uncert is not None:
+                pred_disp, uncert_map = pred_disp
+                if uncert["save_path"] is not None:
+                    kept_uncerts.append(uncert_map)
             n = pred_disp.shape[0]
             if save_path is not None:
                 kept.append(pred_disp)
@@ -578,20 +680,30 @@ def _evaluate_kitti(opt, source, save_path, no_eval, gt_depths, split_dir, devic
             rows.append(depth_metrics(pred_disp, gts, list(range(first, first + n)), min_depth=1e-3, max_depth=80.0,
                                       pred_is_disp=True, median="numpy", median_scaling=median_scaling,
                                       scale_factor=scale, backend=backend))
+            if uncert is not None:
+                spars.append(ops.sparsification(pred_disp, uncert_map, gts, list(range(first, first + n)), rows[-1],
+                                                intervals=uncert["intervals"], min_depth=1e-3, max_depth=80.0,
+                                                scale_factor=scale, median_scaling=median_scaling, backend=backend))
             if clouds is not None:
                 clouds.batch(pred_disp, gts, first, rows[-1], None, 1e-3, 80.0, scale, median_scaling)
             first += n
     if save_path is not None:
         _save_disps(kept, save_path)
+    if kept_uncerts:
+        print("-> Saving predicted uncertainties to ", uncert["save_path"])
+        np.save(uncert["save_path"], torch.cat(kept_uncerts).float().cpu().numpy())
     if clouds is not None:
         clouds.done()
     rows = torch.cat(rows)
     if ground is not None:                                # the ground rows travel with the metrics rows
         rows = torch.cat([rows, torch.cat(ground_rows)], 1)
+    if uncert is not None:                                # so do the sparsification rows: float32 widens exactly
+        rows = torch.cat([rows.double(), torch.cat(spars)], 1)
     rows = rows.cpu().numpy().astype(np.float64)                     # the only host synchronisation of the scoring
     assert first == len(gts), "split has %d images, ground truth %d" % (first, len(gts))
     if ground is not None:
         return _ground_summary(rows[:, :EVAL_OUT], rows[:, EVAL_OUT:])
+    rows, spars = rows[:, :EVAL_OUT], rows[:, EVAL_OUT:]
     mean_errors = rows[:, :7].mean(0)
     ratios = rows[:, 7] if median_scaling else None
     if median_scaling:
@@ -599,6 +711,8 @@ def _evaluate_kitti(opt, source, save_path, no_eval, gt_depths, split_dir, devic
         print(" Scaling ratios | med: {:0.3f} | std: {:0.3f}".format(med, np.std(ratios / med)))
     print("\n  " + ("{:>8} | " * 7).format("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3"))
     print(("&{: 8.3f}  " * 7).format(*mean_errors.tolist()) + "\\\\")
+    if uncert is not None:
+        return mean_errors, ratios, _uncert_summary(spars, uncert)
     return mean_errors, ratios
 
 

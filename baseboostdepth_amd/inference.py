@@ -131,12 +131,16 @@ class DepthPredictor:
             else:
                 disp = self.disparity(x)
             self.last_disp = disp                                              # kept for inspection (tests)
-            colour, floats, stats = ops.disp_viz(disp, sizes, self.min_depth, self.max_depth, 95.0, want_float,
-                                                 self.backend)
-            buffers = [ops.viz_buffer(colour), stats] + ([ops.viz_buffer(floats)] if want_float else [])
-            host = [_to_host(b) for b in buffers]
-            if self.device.type == "cuda":
-                torch.cuda.current_stream(self.device).synchronize()
+            return self._pictures(disp, sizes, want_float)
+
+    def _pictures(self, disp, sizes, want_float, raw=False):
+        """`ops.disp_viz` of network-size maps at the pictures' own sizes, brought to the host in one go: the results."""
+        colour, floats, stats = ops.disp_viz(disp, sizes, self.min_depth, self.max_depth, 95.0, want_float, self.backend,
+                                             raw=raw)
+        buffers = [ops.viz_buffer(colour), stats] + ([ops.viz_buffer(floats)] if want_float else [])
+        host = [_to_host(b) for b in buffers]
+        if self.device.type == "cuda":
+            torch.cuda.current_stream(self.device).synchronize()
         col_h, stats_h = host[0].numpy(), host[1].numpy()
         flt_h = host[2].numpy() if want_float else None
         results, off = [], 0
@@ -147,6 +151,23 @@ class DepthPredictor:
             results.append(DepthPrediction(col, stats_h[i, 0], stats_h[i, 1], sd))
             off += ops.viz_granule(npx)
         return results
+
+    def predict_uncertainty(self, images, want_float=False):
+        """`predict(images, post_process=True)` and what the flip pass knows about it: the batch goes through the networks
+        with its flipped copy, ONE `ops.post_process_uncert` launch gives the blended disparities and their disagreement
+        |d - flip(d')|.  Returns (results, uncertainties): the results of `predict`, and per image the
+        uncertainty map at the picture's own size - `color` magma between its minimum and maximum, `scaled_disp` (with
+        `want_float`) the map itself.  `last_disp` holds the blend, `last_uncert` the map at network size."""
+        if not len(images):
+            return [], []
+        sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
+        with torch.no_grad():
+            self.encoder.eval()
+            self.decoder.eval()
+            x = self.prepare(images)
+            disp, uncert = ops.post_process_uncert(self.disparity(torch.cat((x, torch.flip(x, [3])), 0)), self.backend)
+            self.last_disp, self.last_uncert = disp, uncert
+            return self._pictures(disp, sizes, want_float), self._pictures(uncert, sizes, want_float, raw=True)
 
     def _scaled_disparity(self, images, post_process):
         """(uploaded images, the scaled disparity min_disp + (max_disp - min_disp) * disp at network size [n,.,h,w])."""
@@ -293,6 +314,9 @@ def parse_args(argv=None):
     parser.add_argument("--batch_size", type=int, default=16, help="images per device batch")
     parser.add_argument("--post_process", action="store_true",
                         help="blend the prediction with that of the flipped image (Monodepth2's post-processing)")
+    parser.add_argument("--uncertainty", action="store_true",
+                        help="also write <name>_Base_uncert.jpg: the disagreement of the prediction and the prediction "
+                             "of the mirrored image (implies --post_process); with --save_npy also <name>_uncert.npy")
     parser.add_argument("--point_cloud", action="store_true",
                         help="also write <name>_Base.ply: the coloured point cloud of the prediction (binary PLY)")
     parser.add_argument("--cloud_scale", type=float, default=1.0,
@@ -320,7 +344,7 @@ def parse_args(argv=None):
                         help="horizontal field of view of the camera in degrees (default: the KITTI intrinsics)")
     camera.add_argument("--intrinsics", type=float, nargs=4, default=None, metavar=("FX", "FY", "CX", "CY"),
                         help="the camera's intrinsics in pixels of the input image")
-    parser.epilog = ("Inputs whose names end in _disp.jpg or _Base.jpg are skipped, so that a second run over a "
+    parser.epilog = ("Inputs whose names end in _disp.jpg, _Base.jpg or _Base_uncert.jpg are skipped, so that a second run over a "
                      "folder of jpg files does not colour its own outputs.")
     args = parser.parse_args(argv)
     if args.cloud_stride < 1:
@@ -351,7 +375,7 @@ def find_inputs(image_path, save_path, ext):
         paths, out_dir = sorted(glob.glob(os.path.join(image_path, "*.{}".format(ext)))), save_path
     else:
         raise Exception("Can not find args.image_path: {}".format(image_path))
-    paths = [p for p in paths if not (p.endswith("_disp.jpg") or p.endswith("_Base.jpg"))]
+    paths = [p for p in paths if not p.endswith(("_disp.jpg", "_Base.jpg", "_Base_uncert.jpg"))]
     return paths, out_dir
 
 
@@ -368,6 +392,16 @@ def _save(out_dir, path, result, save_npy):
     pil.fromarray(result.color).save(dest)
     if save_npy:
         np.save(os.path.join(out_dir, "{}_disp.npy".format(stem)), result.scaled_disp)
+    return dest
+
+
+def _save_uncert(out_dir, path, result, save_npy):
+    import PIL.Image as pil
+    stem = os.path.splitext(os.path.basename(path))[0]
+    dest = os.path.join(out_dir, "{}_Base_uncert.jpg".format(stem))
+    pil.fromarray(result.color).save(dest)
+    if save_npy:
+        np.save(os.path.join(out_dir, "{}_uncert.npy".format(stem)), result.scaled_disp)
     return dest
 
 
@@ -440,14 +474,18 @@ def run_cli(args, predictor=None):
             images = list(loads[k])
             if k + 1 < len(chunks):
                 loads.append(pool.map(_load, chunks[k + 1]))
-            if getattr(args, "post_process", False):        # an injected predictor meets the keyword only when it is set
+            if getattr(args, "uncertainty", False):         # an injected predictor meets the method only when it is set
+                results, uncerts = predictor.predict_uncertainty(images, want_float=args.save_npy)
+                cloud_saves += [pool.submit(_save_uncert, out_dir, p, u, args.save_npy) for p, u in zip(chunk, uncerts)]
+            elif getattr(args, "post_process", False):      # an injected predictor meets the keyword only when it is set
                 results = predictor.predict(images, want_float=args.save_npy, post_process=True)
             else:
                 results = predictor.predict(images, want_float=args.save_npy)
             pending += [pool.submit(_save, out_dir, p, r, args.save_npy) for p, r in zip(chunk, results)]
             if getattr(args, "point_cloud", False):
                 kw = dict(inv_K=_cloud_inv_K(args, images), scale=args.cloud_scale, max_depth=args.cloud_max_depth,
-                          stride=args.cloud_stride, post_process=bool(getattr(args, "post_process", False)))
+                          stride=args.cloud_stride,
+                          post_process=bool(getattr(args, "post_process", False) or getattr(args, "uncertainty", False)))
                 if getattr(args, "cloud_view", None) is not None:        # as above: the keywords only when they are set
                     kw.update(view=tuple(args.cloud_view), view_size=getattr(args, "cloud_view_size", 3))
                 camera_height = getattr(args, "camera_height", None)

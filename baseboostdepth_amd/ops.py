@@ -2409,6 +2409,80 @@ def post_process_disp(disp, backend=None):
     return out
 
 
+# ---------------------------------------------------------------------------- uncertainty of the flip pass, sparsification
+def post_process_uncert(disp, backend=None):
+    """`post_process_disp` and the disagreement it throws away, in ONE `bbd_post_process_uncert` launch: `disp` as that
+    function takes it.  Returns (out, uncert), float32 [n,h,w] each: the bytes `post_process_disp` returns, and
+    |disp[i] - flip(disp[n+i])|, the "Post" uncertainty of Poggi et al.."""
+    backend = backend or default_backend()
+    disp = disp.detach()
+    if disp.dim() == 4:
+        assert disp.shape[1] == 1
+        disp = disp[:, 0]
+    if disp.dim() != 3:
+        raise ValueError("post_process_uncert: disp must be [2n,1,h,w] or [2n,h,w], got %s" % (tuple(disp.shape),))
+    if disp.shape[0] < 2 or disp.shape[0] % 2:
+        raise ValueError("post_process_uncert: the leading dimension holds n predictions and their n flipped twins; "
+                         "%d is not a positive even number" % disp.shape[0])
+    disp = disp.contiguous().float()
+    backend._check(disp)
+    n, h, w = disp.shape[0] // 2, disp.shape[1], disp.shape[2]
+    out = torch.empty(n, h, w, dtype=torch.float32, device=disp.device)
+    uncert = torch.empty(n, h, w, dtype=torch.float32, device=disp.device)
+    backend.run("bbd_post_process_uncert", disp, ptr(disp), ptr(out), ptr(uncert), n, h, w)
+    return out, uncert
+
+
+def sparsification_scratch_bytes(desc_host, n):
+    """Bytes of scratch `bbd_sparsification` needs for the `n` BBD_EVAL_DESC rows `desc_host` (a host array): the
+    formula of include/bbd_hip.h over the areas of the crop windows cut to their maps."""
+    d = np.asarray(desc_host).reshape(-1, _lib.EVAL_DESC).astype(np.int64)
+    assert d.shape[0] == n
+    rows = np.maximum(np.minimum(d[:, 5], d[:, 2]) - np.maximum(d[:, 4], 0), 0)
+    cols = np.maximum(np.minimum(d[:, 7], d[:, 3]) - np.maximum(d[:, 6], 0), 0)
+    return _lib.SPARS_SCRATCH_CALL + n * _lib.SPARS_SCRATCH_IMAGE + int((rows * cols).sum()) * _lib.SPARS_SCRATCH_PIXEL
+
+
+def sparsification(pred_disp, uncert, gts, indices, rows, intervals=50, min_depth=1e-3, max_depth=80.0, scale_factor=1.0,
+                   median_scaling=True, backend=None):
+    """How good is an uncertainty map (Poggi et al., CVPR 2020)?  `pred_disp` ([n,1,h,w] or [n,h,w]) is the scaled
+    disparity `evaluation.depth_metrics` was given with `pred_is_disp=True`, `rows` that call's output and `uncert`
+    ([n,h,w]) the uncertainty of every disparity.  The pixels the metrics score are removed in order of falling
+    uncertainty and the rest is re-scored at `intervals` fractions; the same with the three oracle orderings.  One
+    `bbd_sparsification` call, no host synchronisation.  Returns float64 [n, 8 + 6 * (intervals + 1)] on the device:
+    {AUSE abs_rel, rmse, a1, AURG abs_rel, rmse, a1, N, 0}, then the curves [sparse, oracle][abs_rel, rmse, a1]
+    [intervals + 1].  An image without a scored pixel has a row of NaN with N = 0."""
+    backend = backend or default_backend()
+    if not 1 <= int(intervals) <= _lib.SPARS_MAX_INTERVALS:
+        raise ValueError("sparsification: intervals must be 1 ... %d, got %r" % (_lib.SPARS_MAX_INTERVALS, intervals))
+    pred = pred_disp.detach()
+    if pred.dim() == 4:
+        assert pred.shape[1] == 1
+        pred = pred[:, 0]
+    pred = pred.contiguous().float()
+    uncert = uncert.detach()
+    if uncert.dim() == 4:
+        assert uncert.shape[1] == 1
+        uncert = uncert[:, 0]
+    uncert = uncert.contiguous().float()
+    if pred.dim() != 3 or uncert.shape != pred.shape:
+        raise ValueError("sparsification: pred_disp and uncert must both be [n,h,w], got %s and %s"
+                         % (tuple(pred.shape), tuple(uncert.shape)))
+    b = _GtBatch(gts, indices)
+    n, h, w = pred.shape
+    assert n == len(b.idx)
+    assert rows.dtype == torch.float32 and tuple(rows.shape) == (n, _lib.EVAL_OUT) and rows.is_contiguous()
+    backend._check(pred, uncert, gts.buffer, rows)
+    dev, K = pred.device, int(intervals)
+    nbytes = sparsification_scratch_bytes(gts.desc_host[b.idx], n)
+    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    out = torch.empty(n, _lib.SPARS_SUMMARY + 6 * (K + 1), dtype=torch.float64, device=dev)
+    backend.run("bbd_sparsification", pred, ptr(pred), ptr(uncert), ptr(b.gt), ptr(b.desc), ptr(rows), ptr(out),
+                ptr(scratch), nbytes, n, h, w, K, float(min_depth), float(max_depth), float(scale_factor),
+                0 if median_scaling else _lib.EVAL_NO_MEDIAN_SCALING)
+    return out
+
+
 # ---------------------------------------------------------------------------- training-log panel
 _PANEL_LUTS = {}
 

@@ -71,10 +71,54 @@ _FLAGS = [
     # reference), or the camera's height above the pixels found to be road, without ground truth
     ("--scale_recovery", dict(type=str, default="median", choices=["median", "ground"])),
     ("--camera_height", dict(type=float, default=1.65)), ("--ground_angle", dict(type=float, default=5.0)),
+    # evaluate_depth.py: a ground-truth-free uncertainty map of every prediction, judged by sparsification (AUSE / AURG,
+    # DESIGN.md 6n).  post = |d - flip(d')| of the flip pass (implies --post_process); --ext_uncert_to_eval supplies the
+    # maps of --ext_disp_to_eval instead
+    ("--uncertainty", dict(type=str, default="none", choices=["none", "post"])),
+    ("--ext_uncert_to_eval", dict(type=str, default=None, metavar="FILE.npy")),
+    ("--save_pred_uncerts", dict(action="store_true")),
+    ("--sparsification_intervals", dict(type=int, default=50)),
+    ("--save_sparsification", dict(type=str, default=None, metavar="FILE.json")),
 ]
 # other zoos / datasets of the reference: parsed, refused when set
 _OUT_OF_SCOPE = ["--SYNS_eval", "--SQL", "--SQL_L", "--CA_depth", "--DIFFNet", "--stereo_guide",
                  "--x_min", "--png", "--use_stereo", "--eval_eigen_to_benchmark"]
+
+
+SPARSIFICATION_MAX_INTERVALS = 100      # BBD_SPARS_MAX_INTERVALS of include/bbd_hip.h
+
+
+def uncertainty_conflict(opt):
+    """What the uncertainty options of `opt` collide with, as one sentence, or None.  Every field is read with its
+    default, so an `opt` without them has no conflict.  `options.parse` and `evaluation.evaluate` both refuse with it."""
+    get = lambda name, default: getattr(opt, name, default)      # noqa: E731
+    mode, ext_uncert = get("uncertainty", "none"), get("ext_uncert_to_eval", None)
+    if mode not in ("none", "post"):
+        return "uncertainty is none or post, got %r" % (mode,)
+    on = mode == "post" or ext_uncert is not None
+    if not on:
+        for name in ("save_pred_uncerts", "save_sparsification"):
+            if get(name, None):
+                return "%s needs an uncertainty: uncertainty post or ext_uncert_to_eval" % name
+        return None
+    if ext_uncert is not None and mode == "post":
+        return "ext_uncert_to_eval supplies the uncertainty maps and uncertainty post computes them: choose one"
+    if ext_uncert is not None and get("ext_disp_to_eval", None) is None:
+        return "ext_uncert_to_eval holds the uncertainties of the disparities of ext_disp_to_eval, which is not set"
+    if mode == "post" and get("ext_disp_to_eval", None) is not None:
+        return ("uncertainty post comes from the flip pass of the networks, and ext_disp_to_eval runs none: give the maps "
+                "with ext_uncert_to_eval")
+    if ext_uncert is not None and get("save_pred_uncerts", False):
+        return "save_pred_uncerts saves predicted uncertainties, and ext_uncert_to_eval predicts none"
+    for name, set_ in (("eval_split SYNS", get("eval_split", "eigen") == "SYNS"), ("no_eval", bool(get("no_eval", False))),
+                       ("scale_recovery ground", get("scale_recovery", "median") == "ground")):
+        if set_:
+            return ("an uncertainty map is judged on the pixels and with the scale of the KITTI metrics rows: it "
+                    "excludes %s" % name)
+    K = get("sparsification_intervals", 50)
+    if not isinstance(K, int) or not 1 <= K <= SPARSIFICATION_MAX_INTERVALS:
+        return "sparsification_intervals must be 1 ... %d, got %r" % (SPARSIFICATION_MAX_INTERVALS, K)
+    return None
 
 
 class MonodepthOptions:
@@ -159,6 +203,9 @@ class MonodepthOptions:
                                       "height above the road: it excludes %s" % flag)
             if not self.options.camera_height > 0 or not 0.0 <= self.options.ground_angle < 90.0:
                 self.parser.error("--camera_height must be positive and --ground_angle lie in [0, 90) degrees")
+        conflict = uncertainty_conflict(self.options)
+        if conflict:
+            self.parser.error(conflict)
         if self.options.rand and not self.options.no_step_graph:
             self.options.step_graph = True
         if self.options.early_pose_rows != "max":

@@ -55,8 +55,9 @@ extern "C" {
  * 19 = bbd_disp_head_fwd / _bwd (the disparity head with its sigmoid inside);
  * 20 = bbd_depth_consistency (depth-pose geometric consistency: a score and a filter for the scene map);
  * 21 = bbd_stem_* (the encoder stem: BatchNorm + ReLU + max-pool in one pass each way);
- * 22 = bbd_upcat_pad_act_* / bbd_bias_elu_pad_* (the depth decoder's bias + ELU inside its pad / up-sample passes). */
-#define BBD_ABI_VERSION 22
+ * 22 = bbd_upcat_pad_act_* / bbd_bias_elu_pad_* (the depth decoder's bias + ELU inside its pad / up-sample passes);
+ * 23 = bbd_post_process_uncert / bbd_sparsification (depth uncertainty from the flip pass and its AUSE / AURG scores). */
+#define BBD_ABI_VERSION 23
 
 /* Source frames live in separate tensors, one per frame id (inputs[("color", f, 0)],
  * trainer.py:428).  A "slot" indexes a host array of their base pointers. */
@@ -752,6 +753,55 @@ int bbd_view_resolve(const uint64_t* cells, int H, int W, int background_rgb, ui
  * launch, no LDS, no atomics, no host synchronisation; identical calls give identical bytes.  A NULL pointer or n, h
  * or w below 1 returns BBD_E_BADARG and launches nothing. */
 int bbd_post_process_disp(const float* disp, float* out, int n, int h, int w, void* stream);
+
+/* ---- Depth uncertainty from the flip pass and its sparsification scores (csrc/bbd_uncert.hip, ops.post_process_uncert,
+ * ops.sparsification; Poggi et al., CVPR 2020).  Arithmetic and the order of every addition:
+ * csrc/bbd_uncert_math.h.
+ *
+ * bbd_post_process_uncert - bbd_post_process_disp with one more plane, in ONE launch: `out` has the bytes that call
+ * writes, and uncert [n,h,w] = fabsf(disp[i][y][x] - disp[n+i][y][w-1-x]), one float32 subtraction ("Post").  A NULL
+ * pointer or n, h or w below 1 returns BBD_E_BADARG and launches nothing.
+ *
+ * bbd_sparsification - how good is an uncertainty map?  pred and uncert are float32 [n,h,w]: the scaled disparity
+ * bbd_depth_metrics was given with BBD_EVAL_PRED_IS_DISP and its uncertainty; gt, desc and rows are what bbd_error_map
+ * takes (rows [n, BBD_EVAL_OUT]: rows[i][7], the median-scaling ratio, is read on the device).  The pixels of image i are
+ * the N pixels bbd_depth_metrics scores (inside the crop window cut to the map, min_depth < g < max_depth in float32),
+ * in the order of y * GW + x.  Per pixel, in float32:
+ *   p = bbd_eval_resample(pred[i], ..., BBD_EVAL_PRED_IS_DISP, y, x) [* ratio unless BBD_EVAL_NO_MEDIAN_SCALING], clamped
+ *   df = g - p;  e_abs = fabsf(df) / g;  e_sq = df * df;  th = max(g / p, p / g);  a1 = th < 1.25f
+ *   u = the cv2-style linear resize of uncert[i] at (y, x): the taps and weights of the disparity, no reciprocal
+ * Four orderings of the N pixels - by u, e_abs, e_sq, th - each by the monotone order key of the float (every NaN first
+ * made 0x7fc00000, -0 made +0: a NaN ranks above +inf) DESCENDING, pixel order ascending among equal keys.  With
+ * K = intervals and r_k = floor(k * N / K), S_k is what remains after the first r_k pixels of an ordering, and
+ *   abs_rel_k = sum(e_abs) / |S_k|   rmse_k = sqrt(sum(e_sq) / |S_k|)   a1_k = #a1 / |S_k|       k < K, in float64
+ * point K is 0, 0, 1; trapz(c) = (sum over k < K of (c_k + c_(k+1)) / 2) / K.  `sparse` is a metric's curve under the u
+ * ordering, `oracle` under its own.  out is float64 [n, BBD_SPARS_SUMMARY + 6 * (K + 1)]:
+ *   {AUSE abs_rel, AUSE rmse, AUSE a1, AURG abs_rel, AURG rmse, AURG a1, N, 0}, then curves [2: sparse, oracle][3][K + 1]
+ *   AUSE = trapz(sparse) - trapz(oracle), AURG = sparse_0 - trapz(sparse); both signs flipped for a1 (higher is better)
+ * An image with N = 0 gets quiet NaNs with N = 0; a NaN prediction propagates as in bbd_depth_metrics.  The sums are
+ * float64 in an order that depends on N and K alone, the sort is a stable segmented radix sort: no atomics on floats or
+ * on positions, no allocation, no host synchronisation - identical calls give identical bytes.
+ *
+ * scratch is the caller's, 8-byte aligned, needs no initialisation, and scratch_bytes states its capacity - the call
+ * cannot read the windows on the host:
+ *   scratch_bytes = BBD_SPARS_SCRATCH_CALL + n * BBD_SPARS_SCRATCH_IMAGE + P * BBD_SPARS_SCRATCH_PIXEL
+ * with P at least the sum over the n desc rows of the area of the crop window cut to the map,
+ * max(0, min(r1, GH) - max(r0, 0)) * max(0, min(c1, GW) - max(c0, 0)).  A scratch_bytes that is not of this form for a
+ * whole P >= 0 is refused.  Launches are sized by P; should the windows on the device exceed P, nothing is sorted and
+ * every row is NaN, N included.
+ *
+ * Returns BBD_E_BADARG and launches nothing for a NULL pointer, n outside [1, 65535], h or w below 1, intervals outside
+ * [1, BBD_SPARS_MAX_INTERVALS], a flag other than BBD_EVAL_NO_MEDIAN_SCALING, a scratch that is misaligned or too small
+ * (not of the form above) or P beyond 2^31 - 2049. */
+#define BBD_SPARS_MAX_INTERVALS 100
+#define BBD_SPARS_SUMMARY 8
+#define BBD_SPARS_SCRATCH_PIXEL 81
+#define BBD_SPARS_SCRATCH_IMAGE 8916
+#define BBD_SPARS_SCRATCH_CALL 128
+int bbd_post_process_uncert(const float* disp, float* out, float* uncert, int n, int h, int w, void* stream);
+int bbd_sparsification(const float* pred, const float* uncert, const float* gt, const int32_t* desc, const float* rows,
+                       double* out, void* scratch, long scratch_bytes, int n, int h, int w, int intervals,
+                       double min_depth, double max_depth, double scale_factor, int flags, void* stream);
 
 /* ---- KITTI odometry evaluation (evaluate_pose.py:18-41, :101-116, :125-159): everything after the pose
  * network, for all windows of a sequence in one call - three small launches, no host synchronisation, no atomics
