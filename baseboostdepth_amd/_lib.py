@@ -23,6 +23,8 @@ PROTOTYPES, CONSTANTS = _abi.read_header()
 SIGNATURES = {name: [ctype for ctype, _ in proto.params] for name, proto in PROTOTYPES.items()}
 globals().update(CONSTANTS)
 TRAJ_MODES = {mode.lower(): CONSTANTS["TRAJ_" + mode] for mode in ("SIM3", "SE3", "SCALE", "NONE")}
+# the host-side queries of bbd_conv3x3_wgrad have a header of their own (include/bbd_wgrad.h says why), read the same way
+WGRAD_HELPERS, _ = _abi.read_header(os.path.join(os.path.dirname(_abi.HEADER), "bbd_wgrad.h"))
 
 
 class HipLibrary:
@@ -42,6 +44,10 @@ class HipLibrary:
                 # the host-side helpers, under their ABI name minus `bbd_`: lib.num_tiles(H, W), lib.map_state_bytes(T);
                 # one without parameters is a constant of the build and is bound as its value: lib.tile_w, lib.smooth_chunks
                 setattr(self, name[len("bbd_"):], fn if proto.params else fn())
+        for name, proto in WGRAD_HELPERS.items():
+            fn = getattr(self._dll, name)
+            fn.argtypes, fn.restype = [ctype for ctype, _ in proto.params], proto.restype
+            setattr(self, name[len("bbd_"):], fn)
         # the shorter names the depth-wise weight-gradient helpers had before the binding was read from the header; callers
         # outside the package (tests/test_gpu_vit_f64.py) still use them
         self.dwconv_wgrad_scratch_floats = self.dwconv_tokens_wgrad_scratch_floats

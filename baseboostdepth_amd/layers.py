@@ -125,8 +125,12 @@ class ConvBlock(nn.Module):
         return self.nonlin(conv(xp))
 
     def conv_raw(self, xp):
-        """The bias-free convolution of the padded input: what `bias_act_` and the decoder's fused glue start from."""
-        return torch.nn.functional.conv2d(xp, self.conv.conv.weight, None)
+        """The bias-free convolution of the padded input: what `bias_act_` and the decoder's fused glue start from.
+        The measured fine-scale shapes take their weight gradient from the NCHW tensors (`ops.conv3x3_valid`)."""
+        weight = self.conv.conv.weight
+        if ops.conv3x3_wgrad_routed(xp, weight):
+            return ops.conv3x3_valid(xp, weight)
+        return torch.nn.functional.conv2d(xp, weight, None)
 
     def bias_act_(self, y):
         """bias + ELU on `conv_raw`'s result (H * W a multiple of 4), in place where the HIP pass takes it."""

@@ -1663,6 +1663,87 @@ def bias_elu_pad(conv_out, bias, backend=None):
     return _BiasEluPad.apply(conv_out, bias, backend or default_backend())
 
 
+# ---------------------------------------------------------------------------- ConvBlock weight gradients from NCHW
+# 0: every weight gradient stays with MIOpen, as before (A/B runs)
+FUSED_WGRAD = os.environ.get("BBD_FUSED_WGRAD", "1") != "0"
+
+# (C, K, H, W) of a ConvBlock convolution - input channels, output channels, output size - whose weight gradient
+# `bbd_conv3x3_wgrad` takes, at any batch size.  A row is here because tools/wgrad_bench.py measured the call's slowest
+# repeat faster than MIOpen's fastest at batch 12 (profiles/decoder_wgrad/wgrad_bench.json); every other shape stays with
+# MIOpen, those the kernel supports but was not measured on included.
+WGRAD_ROUTES = {
+    (16, 16, 192, 640),     # DepthDecoder upconv(0,1) at 640 x 192: 1.8 x MIOpen's call
+    (32, 16, 96, 320),      # upconv(0,0): 1.7 x
+}                           # not here: upconv(1,0) (64, 32, 48, 160), within 10 % either way; upconv(1,1), slower
+
+
+def conv3x3_wgrad_shape(xp, w):
+    """(N, C, K, H, W) of `bbd_conv3x3_wgrad` for the padded input `xp` and the weight `w`, or None where the call does
+    not take them: contiguous fp32 GPU tensors, a [K,C,3,3] weight."""
+    if not (xp.dim() == 4 and w.dim() == 4 and _glue_tensor(xp) and _glue_tensor(w)):
+        return None
+    N, C, Hp, Wp = xp.shape
+    if w.shape != (w.shape[0], C, 3, 3) or Hp < 3 or Wp < 3:
+        return None
+    return N, C, w.shape[0], Hp - 2, Wp - 2
+
+
+def conv3x3_wgrad_routed(xp, w, backend=None):
+    """Does the weight gradient of `F.conv2d(xp, w)` go to `bbd_conv3x3_wgrad`?  Only for the measured rows of
+    WGRAD_ROUTES, and never with BBD_FUSED_WGRAD=0 or BBD_FUSED_NN=0."""
+    if not (FUSED_WGRAD and FUSED_NN):
+        return False
+    shape = conv3x3_wgrad_shape(xp, w)
+    if shape is None or shape[1:] not in WGRAD_ROUTES:
+        return False
+    return bool((backend or default_backend()).lib.conv3x3_wgrad_supported(*shape))
+
+
+def conv3x3_wgrad(xp, grad_z, K=None, backend=None):
+    """grad_w [K,C,3,3] of `F.conv2d(xp, w)` from xp [N,C,H+2,W+2] and grad_z [N,K,H,W]: two launches, no atomics."""
+    backend = backend or default_backend()
+    backend._check(xp, grad_z)
+    xp, grad_z = xp.contiguous(), grad_z.contiguous()
+    N, C, Hp, Wp = xp.shape
+    K = grad_z.shape[1] if K is None else K
+    H, W = Hp - 2, Wp - 2
+    assert grad_z.shape == (N, K, H, W) and xp.dtype == grad_z.dtype == torch.float32
+    doubles = backend.lib.conv3x3_wgrad_scratch_doubles(N, C, K, H, W)
+    if doubles <= 0:
+        raise _lib.BbdError("bbd_conv3x3_wgrad does not take N=%d C=%d K=%d H=%d W=%d" % (N, C, K, H, W))
+    scratch = torch.empty(doubles, device=xp.device, dtype=torch.float64)
+    grad_w = torch.empty(K, C, 3, 3, device=xp.device, dtype=torch.float32)
+    backend.run("bbd_conv3x3_wgrad", xp, ptr(xp), ptr(grad_z), ptr(grad_w), ptr(scratch), N, C, K, H, W)
+    return grad_w
+
+
+class _Conv3x3Valid(torch.autograd.Function):
+    """`F.conv2d(xp, w)` of a padded input whose weight gradient comes from `bbd_conv3x3_wgrad`; forward and data gradient
+    are MIOpen's, the same problems as without this function."""
+
+    @staticmethod
+    def forward(ctx, xp, w, backend):
+        ctx.save_for_backward(xp, w)
+        ctx.backend = backend
+        return torch.nn.functional.conv2d(xp, w, None)
+
+    @staticmethod
+    def backward(ctx, grad_z):
+        xp, w = ctx.saved_tensors
+        grad_x = grad_w = None
+        if ctx.needs_input_grad[0]:
+            grad_x = torch.ops.aten.convolution_backward(grad_z, xp, w, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
+                                                         [True, False, False])[0]
+        if ctx.needs_input_grad[1]:
+            grad_w = conv3x3_wgrad(xp, grad_z, w.shape[0], ctx.backend)
+        return grad_x, grad_w, None
+
+
+def conv3x3_valid(xp, w, backend=None):
+    """`F.conv2d(xp, w)` for a pair `conv3x3_wgrad_routed` accepts."""
+    return _Conv3x3Valid.apply(xp, w, backend or default_backend())
+
+
 # ---------------------------------------------------------------------------- disparity head Conv3x3(C -> 1)
 class _DispConv(torch.autograd.Function):
     @staticmethod

@@ -56,8 +56,9 @@ extern "C" {
  * 20 = bbd_depth_consistency (depth-pose geometric consistency: a score and a filter for the scene map);
  * 21 = bbd_stem_* (the encoder stem: BatchNorm + ReLU + max-pool in one pass each way);
  * 22 = bbd_upcat_pad_act_* / bbd_bias_elu_pad_* (the depth decoder's bias + ELU inside its pad / up-sample passes);
- * 23 = bbd_post_process_uncert / bbd_sparsification (depth uncertainty from the flip pass and its AUSE / AURG scores). */
-#define BBD_ABI_VERSION 23
+ * 23 = bbd_post_process_uncert / bbd_sparsification (depth uncertainty from the flip pass and its AUSE / AURG scores);
+ * 24 = bbd_conv3x3_wgrad (the decoder's 3x3 weight gradients from the NCHW tensors). */
+#define BBD_ABI_VERSION 24
 
 /* Source frames live in separate tensors, one per frame id (inputs[("color", f, 0)],
  * trainer.py:428).  A "slot" indexes a host array of their base pointers. */
@@ -1065,6 +1066,23 @@ int bbd_upcat_pad_act_bwd(const float* grad_out, const float* z, const float* bi
 int bbd_bias_elu_pad_fwd(float* y, const float* bias, float* yp, int N, int C, int H, int W, void* stream);
 int bbd_bias_elu_pad_bwd(const float* grad_yp, const float* grad_y, const float* y, float* grad_z, float* grad_bias,
                          double* scratch, int scratch_doubles, int N, int C, int H, int W, void* stream);
+
+/* Weight gradient of a ConvBlock's 3x3, stride-1 convolution of an input that already carries its border (DepthDecoder
+ * `upconv` layers), straight from the NCHW tensors: no transposed copies, no atomics, nothing zeroed first.
+ *   xp [N, C, H+2, W+2], grad_z [N, K, H, W], grad_w [K, C, 3, 3] (written, not accumulated), all contiguous fp32:
+ *   grad_w[k][c][r][s] = sum over (n, y, x) of grad_z[n][k][y][x] * xp[n][c][y + r][x + s].
+ * Numerics: v_mfma_f32_16x16x4_f32 is an exact fp32 fma chain.  Every fp32 accumulator takes at most BBD_WGRAD_RUN
+ * products and is then widened; the widened values are added as doubles in a fixed order (per workgroup, then over the
+ * workgroups by a second launch), so |grad_w - exact| <= (BBD_WGRAD_RUN + 1) * 2^-24 * sum |grad_z| |xp| element by
+ * element, and two calls on the same inputs give the same bits.
+ * The call's two host-side queries are declared in include/bbd_wgrad.h.  bbd_conv3x3_wgrad_supported: 1 where the call
+ * takes the shape - C and K multiples of 16 in 16..1024, N, H, W >= 1, every tensor and the scratch below 2^31
+ * elements - else 0, and the call returns BBD_E_BADARG and launches nothing.  scratch holds
+ * bbd_conv3x3_wgrad_scratch_doubles(N, C, K, H, W) doubles (0: not supported); no element of it is read before the call
+ * has written it. */
+#define BBD_WGRAD_RUN 128
+int bbd_conv3x3_wgrad(const float* xp, const float* grad_z, float* grad_w, double* scratch, int N, int C, int K, int H,
+                      int W, void* stream);
 
 /* ---- MonoViT encoder (BASELINE configs[4]): depth-wise convolution on token-layout activations ----------
  * The position encodings of the reference's MPViT (networksvit/mpvit.py:240-330: ConvPosEnc, ConvRelPosEnc)
