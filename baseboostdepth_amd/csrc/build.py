@@ -40,6 +40,7 @@ SRCS = _here("""
     bbd_map.hip
     bbd_view.hip
     bbd_consist.hip
+    bbd_geo.hip
     bbd_uncert.hip
     bbd_wgrad.hip
 """)

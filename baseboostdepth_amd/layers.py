@@ -159,6 +159,27 @@ class BackprojectDepth(nn.Module):
         return ops.backproject(depth, inv_K, self.height, self.width, backend)
 
 
+class GeometryConsistency(nn.Module):
+    """SC-SfMLearner's geometry-consistency term (Bian et al., NeurIPS 2019) as one differentiable op:
+    sigmoid disparity of the target frames [B,1,H,W], a list of V source disparities of that shape, a list of V
+    target-to-source poses [B,4,4], K and inv_K [B,4,4] -> `ops.GeometryConsistency` (its `loss` is the mean of
+    |z s - 1| / (z s + 1) over the visible samples).  Gradients reach every disparity and every pose."""
+
+    def __init__(self, min_depth, max_depth):
+        super().__init__()
+        self.min_depth, self.max_depth = float(min_depth), float(max_depth)
+
+    def forward(self, disp, source_disps, poses, K, inv_K, want_err=False, want_code=False, backend=None):
+        source_disps, poses = list(source_disps), list(poses)
+        if not source_disps or len(source_disps) != len(poses):
+            raise ValueError("GeometryConsistency: one pose per source disparity is needed, got %d and %d"
+                             % (len(source_disps), len(poses)))
+        q_tgt = disp_to_depth(disp, self.min_depth, self.max_depth)[0][:, 0]
+        q_src = torch.stack([disp_to_depth(d, self.min_depth, self.max_depth)[0][:, 0] for d in source_disps])
+        T = torch.stack([p[:, :3] for p in poses])
+        return ops.geometry_consistency(q_tgt, q_src, T, K, inv_K, want_err, want_code, backend)
+
+
 class Project3D(nn.Module):
     """points [n,4,H*W], K, T [n,4,4] -> sampling grid [n,H,W,2] in [-1,1]  (layers.py:170-195);
     differentiable w.r.t. points, T and K."""

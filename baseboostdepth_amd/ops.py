@@ -2360,6 +2360,98 @@ def depth_consistency(disp, poses, K, inv_K, sources, scale=None, threshold=0.05
     return Consistency(filtered, seen, agree, err, counters, transforms)
 
 
+# ---------------------------------------------------------------------------- geometry-consistency loss (training)
+GeometryConsistency = collections.namedtuple("GeometryConsistency", "loss pair_sum pair_count err code")
+GeometryConsistency.__doc__ = """What `geometry_consistency` leaves on the device: `loss` float64 scalar (differentiable),
+`pair_sum` float64 [V,B] (differentiable), `pair_count` int64 [V,B], `err` float32 [V,B,H,W] or None (0 where the sample
+is not visible), `code` uint8 [V,B,H,W] or None (bit 0 = visible, bit 1 = z s > 1)."""
+
+
+def geo_scratch_words(B, H, W, V, backward):
+    """8-byte words of scratch of bbd_geo_fwd / bbd_geo_bwd: the formulas of include/bbd_hip.h."""
+    items = (H * W + _lib.GEO_RUN - 1) // _lib.GEO_RUN
+    return V * B * H * W + B * items * V * 12 if backward else B * items * V * 2
+
+
+class _GeometryConsistency(torch.autograd.Function):
+    """pair_sum [V,B] of bbd_geo_fwd; bbd_geo_bwd gives the gradients to q_tgt, q_src and T from the upstream gradient
+    on the device.  Nothing is read back either way."""
+
+    @staticmethod
+    def forward(ctx, q_tgt, q_src, T, K, inv_K, want_err, want_code, backend):
+        V, B, H, W = q_src.shape
+        dev = q_tgt.device
+        pair_sum = torch.empty(V, B, dtype=torch.float64, device=dev)
+        pair_count = torch.empty(V, B, dtype=torch.int64, device=dev)
+        err = torch.empty(V, B, H, W, dtype=torch.float32, device=dev) if want_err else None
+        code = torch.empty(V, B, H, W, dtype=torch.uint8, device=dev) if want_code else None
+        words = geo_scratch_words(B, H, W, V, False)
+        scratch = torch.empty(words, dtype=torch.int64, device=dev)
+        backend.run("bbd_geo_fwd", q_tgt, ptr(q_tgt), ptr(q_src), ptr(T), ptr(K), ptr(inv_K), ptr(pair_sum),
+                    ptr(pair_count), ptr(err), ptr(code), ptr(scratch), words, B, H, W, V)
+        ctx.save_for_backward(q_tgt, q_src, T, K, inv_K)
+        ctx.backend = backend
+        outs = [t for t in (pair_count, err, code) if t is not None]
+        ctx.mark_non_differentiable(*outs)
+        return pair_sum, pair_count, err, code
+
+    @staticmethod
+    def backward(ctx, g_sum, *_unused):
+        q_tgt, q_src, T, K, inv_K = ctx.saved_tensors
+        V, B, H, W = q_src.shape
+        g = g_sum.to(torch.float64).contiguous()
+        grad_t, grad_s, grad_T = torch.empty_like(q_tgt), torch.empty_like(q_src), torch.empty_like(T)
+        words = geo_scratch_words(B, H, W, V, True)
+        scratch = torch.empty(words, dtype=torch.int64, device=q_tgt.device)
+        ctx.backend.run("bbd_geo_bwd", q_tgt, ptr(q_tgt), ptr(q_src), ptr(T), ptr(K), ptr(inv_K), ptr(g), ptr(grad_t),
+                        ptr(grad_s), ptr(grad_T), ptr(scratch), words, B, H, W, V)
+        return grad_t, grad_s, grad_T, None, None, None, None, None
+
+
+def geometry_consistency(q_tgt, q_src, T, K, inv_K, want_err=False, want_code=False, backend=None):
+    """The geometry-consistency loss of SC-SfMLearner (Bian et al., NeurIPS 2019) between B target frames
+    and V source frames each: a target pixel is back-projected with its inverse depth `q_tgt` float32 [B,H,W], moved with
+    `T` float32 [V,B,12] (rows 0..2 of the target-to-source matrix; [V,B,3,4] is taken too) and compared with the
+    bilinear sample s of `q_src` float32 [V,B,H,W] there: e = |z s - 1| / (z s + 1), the err `depth_consistency` scores.
+    `K`, `inv_K` float32 [B,16] or [B,4,4], not differentiable.  Returns a `GeometryConsistency`; `loss` is the mean of e
+    over the visible samples (0 where there is none), formed on the device: no host synchronisation, capturable.
+    Gradients reach q_tgt, q_src and T; identical calls give identical bytes."""
+    backend = backend or default_backend()
+    who = "geometry_consistency: "
+    if not torch.is_tensor(q_tgt) or q_tgt.dtype != torch.float32 or q_tgt.dim() != 3:
+        raise ValueError(who + "q_tgt must be float32 [B,H,W], got %s %s"
+                         % (getattr(q_tgt, "dtype", type(q_tgt)), tuple(getattr(q_tgt, "shape", ()))))
+    B, H, W = q_tgt.shape
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError(who + "q_tgt must not be empty, got %s" % (tuple(q_tgt.shape),))
+    if not torch.is_tensor(q_src) or q_src.dtype != torch.float32 or q_src.dim() != 4 \
+            or tuple(q_src.shape[1:]) != (B, H, W) or not 1 <= q_src.shape[0] <= _lib.GEO_MAX_VIEWS:
+        raise ValueError(who + "q_src must be float32 [V,%d,%d,%d] with 1 <= V <= %d, got %s %s"
+                         % (B, H, W, _lib.GEO_MAX_VIEWS, getattr(q_src, "dtype", type(q_src)),
+                            tuple(getattr(q_src, "shape", ()))))
+    V = int(q_src.shape[0])
+    if not torch.is_tensor(T) or T.dtype != torch.float32 or tuple(T.shape) not in ((V, B, 12), (V, B, 3, 4)):
+        raise ValueError(who + "T must be float32 [%d,%d,12] or [%d,%d,3,4], got %s %s"
+                         % (V, B, V, B, getattr(T, "dtype", type(T)), tuple(getattr(T, "shape", ()))))
+    mats = []
+    for m, what in ((K, "K"), (inv_K, "inv_K")):
+        if not torch.is_tensor(m) or m.dtype != torch.float32 or tuple(m.shape) not in ((B, 16), (B, 4, 4)):
+            raise ValueError(who + "%s must be float32 [%d,16] or [%d,4,4], got %s %s"
+                             % (what, B, B, getattr(m, "dtype", type(m)), tuple(getattr(m, "shape", ()))))
+        mats.append(m.detach().reshape(B, 16).contiguous())
+    for t, what in ((q_src, "q_src"), (T, "T"), (mats[0], "K"), (mats[1], "inv_K")):
+        if t.device != q_tgt.device:
+            raise ValueError(who + "%s is on %s, q_tgt on %s" % (what, t.device, q_tgt.device))
+    if H * W > 1 << 23 or V * B * H * W > 0x7fffffff:
+        raise ValueError(who + "%d x %d pairs of %d x %d pixels are more than one call holds" % (V, B, H, W))
+    backend._check(q_tgt, q_src, T, *mats)
+    pair_sum, pair_count, err, code = _GeometryConsistency.apply(
+        q_tgt.contiguous(), q_src.contiguous(), T.reshape(V, B, 12).contiguous(), mats[0], mats[1], bool(want_err),
+        bool(want_code), backend)
+    loss = pair_sum.sum() / pair_count.sum().clamp(min=1)
+    return GeometryConsistency(loss, pair_sum, pair_count, err, code)
+
+
 # ---------------------------------------------------------------------------- views (rasterised points and polylines)
 ViewState = collections.namedtuple("ViewState", "cells counters H W")
 ViewState.__doc__ = """The caller-owned canvas of the `bbd_view_*` entries: `cells` int64 [H,W] (the uint64 keys, empty =

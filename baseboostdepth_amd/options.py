@@ -62,6 +62,10 @@ _FLAGS = [
     # panels = text + pictures rendered on the device (target, disparity, minimum-loss map, arg-min map, the warps)
     ("--train_log", dict(type=str, default="off", choices=["off", "text", "panels"])),
     ("--log_samples", dict(type=int, default=1)),
+    # SC-SfMLearner's geometry-consistency term (Bian et al., NeurIPS 2019): the weight of the loss that makes
+    # the depth of a frame and the depth of its temporal neighbours agree under the predicted motion.  0 = off: the step is
+    # the step it was.  Nothing has been trained with it here: no value is recommended
+    ("--geometry_consistency", dict(type=float, default=0.0, metavar="W")),
     # evaluate_depth.py: write the clouds of the first --cloud_count images of the split, prediction and ground truth, as
     # <index>_pred.ply / <index>_gt.ply into this directory while the batch is in HBM
     ("--save_clouds", dict(type=str, default=None, metavar="DIR")), ("--cloud_count", dict(type=int, default=8)),
@@ -118,6 +122,17 @@ def uncertainty_conflict(opt):
     K = get("sparsification_intervals", 50)
     if not isinstance(K, int) or not 1 <= K <= SPARSIFICATION_MAX_INTERVALS:
         return "sparsification_intervals must be 1 ... %d, got %r" % (SPARSIFICATION_MAX_INTERVALS, K)
+    return None
+
+
+def geometry_consistency_conflict(opt):
+    """One sentence on why the geometry-consistency weight cannot be honoured, or None."""
+    W = getattr(opt, "geometry_consistency", 0.0)
+    if not W >= 0.0:
+        return "--geometry_consistency is the weight of a loss term and must not be negative, got %r" % (W,)
+    if W > 0.0 and (getattr(opt, "rand", False) or getattr(opt, "trimin", False)):
+        return ("--geometry_consistency needs one frame set for the whole batch: with --rand or --trimin the frame sets vary "
+                "per sample and the step runs in pooled form, where the term is not routed")
     return None
 
 
@@ -204,6 +219,9 @@ class MonodepthOptions:
             if not self.options.camera_height > 0 or not 0.0 <= self.options.ground_angle < 90.0:
                 self.parser.error("--camera_height must be positive and --ground_angle lie in [0, 90) degrees")
         conflict = uncertainty_conflict(self.options)
+        if conflict:
+            self.parser.error(conflict)
+        conflict = geometry_consistency_conflict(self.options)
         if conflict:
             self.parser.error(conflict)
         if self.options.rand and not self.options.no_step_graph:

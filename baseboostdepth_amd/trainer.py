@@ -17,7 +17,8 @@ import torch
 import torch.optim as optim
 
 from . import networks, ops, steptables
-from .layers import SSIM, BackprojectDepth, Project3D, disp_to_depth, transformation_from_parameters
+from .layers import (SSIM, BackprojectDepth, GeometryConsistency, Project3D, disp_to_depth,
+                     transformation_from_parameters)
 from .plan import STEREO, canonical_permutation, get_plan, owners_of, sample_max_offsets
 
 
@@ -124,6 +125,13 @@ class Trainer:
         if getattr(opt, "load_weights_folder", "None") not in (None, "None"):
             self.load_model()
 
+        self.geometry_weight = float(getattr(opt, "geometry_consistency", 0.0) or 0.0)
+        if self.geometry_weight > 0.0:
+            from .options import geometry_consistency_conflict
+            conflict = geometry_consistency_conflict(opt)
+            if conflict:
+                raise ValueError(conflict)
+            self.geometry_consistency = GeometryConsistency(opt.min_depth, opt.max_depth)
         self.ssim = SSIM()
         self.backproject_depth = {0: BackprojectDepth(opt.batch_size, opt.height, opt.width)}
         self.project_3d = {0: Project3D(opt.batch_size, opt.height, opt.width)}
@@ -733,6 +741,8 @@ class Trainer:
                             v.record_stream(main)
             outputs.update(self.generate_images_pred(inputs, outputs))
             losses = self.compute_losses(inputs, outputs)
+            if getattr(self, "geometry_weight", 0.0) > 0.0:
+                self.add_geometry_loss(inputs, outputs, losses)
         else:
             outputs = {}
             feats = self.models["encoder"](inputs["color", 0, 0])
@@ -1053,6 +1063,39 @@ class Trainer:
         if self.opt.no_ssim:
             return l1
         return 0.85 * self.ssim(pred, target, backend=self._backend()).mean(1, True) + 0.15 * l1
+
+    def add_geometry_loss(self, inputs, outputs, losses):
+        """`--geometry_consistency W`: SC-SfMLearner's geometry-consistency term between the target frame and every
+        temporal source frame of `opt.frame_ids`.  The depth network runs once more per source frame on
+        `("color_aug", f, 0)` - a call of its own with its own BatchNorm batch statistics, as SC-SfMLearner runs its
+        disparity network - and only `("disp", 0)` of it is used.  Sets `losses["loss/geometry"]` and adds W times it to
+        `losses["loss"]`; gradients reach both depth maps and the pose.  Runs on the main stream after the pose results
+        have joined it; no host synchronisation, so the step still captures."""
+        from .options import geometry_consistency_conflict
+        opt = self.opt
+        conflict = geometry_consistency_conflict(opt)
+        if conflict or self.pooled_step:
+            raise ValueError(conflict or "--geometry_consistency is not routed through the pooled form of the step")
+        frames = [f for f in opt.frame_ids if f != 0 and f != STEREO]
+        if not frames:
+            raise ValueError("--geometry_consistency needs a temporal source frame in --frame_ids, got %r" % (opt.frame_ids,))
+        disp = outputs[("disp", 0)]
+        if tuple(disp.shape[2:]) != (opt.height, opt.width):
+            raise ValueError("--geometry_consistency needs a full-resolution (\"disp\", 0), got %s" % (tuple(disp.shape),))
+        sources, poses = [], []
+        for f in frames:
+            source = self.models["depth"](self.models["encoder"](inputs[("color_aug", f, 0)]))[("disp", 0)]
+            pose = outputs[("cam_T_cam", 0, f)]
+            if source.shape != disp.shape or pose.shape[0] != disp.shape[0]:
+                raise ValueError("--geometry_consistency needs frame %r of every sample of the batch, got %d images and %d "
+                                 "poses for %d samples" % (f, source.shape[0], pose.shape[0], disp.shape[0]))
+            outputs[("disp_source", f)] = source
+            sources.append(source)
+            poses.append(pose)
+        res = self.geometry_consistency(outputs[("disp", 0)], sources, poses, inputs[("K", 0)], inputs[("inv_K", 0)],
+                                        backend=self._backend())
+        losses["loss/geometry"] = res.loss.to(losses["loss"].dtype)
+        losses["loss"] = losses["loss"] + self.geometry_weight * losses["loss/geometry"]
 
     def compute_losses(self, inputs, outputs):
         opt = self.opt

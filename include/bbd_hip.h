@@ -57,8 +57,9 @@ extern "C" {
  * 21 = bbd_stem_* (the encoder stem: BatchNorm + ReLU + max-pool in one pass each way);
  * 22 = bbd_upcat_pad_act_* / bbd_bias_elu_pad_* (the depth decoder's bias + ELU inside its pad / up-sample passes);
  * 23 = bbd_post_process_uncert / bbd_sparsification (depth uncertainty from the flip pass and its AUSE / AURG scores);
- * 24 = bbd_conv3x3_wgrad (the decoder's 3x3 weight gradients from the NCHW tensors). */
-#define BBD_ABI_VERSION 24
+ * 24 = bbd_conv3x3_wgrad (the decoder's 3x3 weight gradients from the NCHW tensors);
+ * 25 = bbd_geo_fwd / bbd_geo_bwd (the geometry-consistency loss for training, forward and backward). */
+#define BBD_ABI_VERSION 25
 
 /* Source frames live in separate tensors, one per frame id (inputs[("color", f, 0)],
  * trainer.py:428).  A "slot" indexes a host array of their base pointers. */
@@ -692,6 +693,48 @@ int bbd_depth_consistency(const float* disp, const double* poses, const double* 
                           const float* inv_K, const int32_t* sources, double* transforms, uint8_t* seen, uint8_t* agree,
                           float* err, float* filtered, int64_t* counters, int n, int h, int w, int V, double threshold,
                           int min_views, int flags, void* stream);
+
+/* ---- Geometry-consistency loss for training (csrc/bbd_geo.hip, ops.geometry_consistency; Bian et al.,
+ * NeurIPS 2019): the err of bbd_depth_consistency as a differentiable loss between a target frame and V source frames of
+ * the SAME batch, with gradients to both inverse-depth maps and to the pose.  Everything float32 on the device:
+ *   q_tgt       [B,H,W]    inverse depth of the target frames (the scaled disparity min_disp + (max_disp - min_disp) disp)
+ *   q_src       [V,B,H,W]  the same of each source frame, 1 <= V <= BBD_GEO_MAX_VIEWS
+ *   T           [V,B,12]   rows 0..2 of the target-to-source 4x4 matrix, row-major
+ *   K, inv_K    [B,16]     4x4 row-major as the batch dictionary holds them; the 3x3 parts are read
+ * Per target pixel (x, y) and source (operation by operation: csrc/bbd_geo_math.h, -ffp-contract=off, float32, one IEEE
+ * operation where written, no transcendental function): p = inv_K [x, y, 1] / q_tgt;  X = R p + t, z = X_2;  c = K X,
+ * u = c_0 / c_2, t = c_1 / c_2.  The sample is VISIBLE when q_tgt > 0 and finite, z finite and above 0.001,
+ * 0 <= u <= W - 1, 0 <= t <= H - 1, the four taps at x0 = min(floor(u), W - 2), y0 = min(floor(t), H - 2) above 0 and finite
+ * (H < 2 or W < 2: nothing is visible), the bilinear sample s of the source's inverse depth at least 2^-10 and a = z s
+ * finite.  e = |a - 1| / (a + 1).
+ *   bbd_geo_fwd
+ *   pair_sum    OUT float64 [V,B]: the sum of e over the pair's visible samples - the integer sum of
+ *               floor(e 2^36 + 0.5), times 2^-36: order-free
+ *   pair_count  OUT int64 [V,B]: its visible samples
+ *   err         OUT float32 [V,B,H,W] or NULL: e, 0 where not visible
+ *   code        OUT uint8 [V,B,H,W] or NULL: bit 0 = visible, bit 1 = a > 1
+ *   scratch     8-byte words, at least B * items * V * 2 with items = ceil(H * W / BBD_GEO_RUN); need not be cleared
+ *   bbd_geo_bwd
+ *   g           float64 [V,B] ON THE DEVICE: the upstream gradient of pair_sum
+ *   grad_q_tgt  OUT float32 [B,H,W]: summed over a pixel's sources in the pixel's lane, in source order
+ *   grad_q_src  OUT float32 [V,B,H,W]: a scatter, added as 64-bit integers of fixed point 2^30 (vector atomics, order-free)
+ *               and converted once.  |de/ds| <= 1 / (2 s) <= 2^9 by the rule s >= 2^-10, a map has at most 2^23 pixels: the
+ *               sums cannot leave the 64-bit range
+ *   grad_T      OUT float32 [V,B,12]: float64 partial sums per work item in a fixed layout, added in a fixed order
+ *   scratch     8-byte words, at least V * B * H * W + B * items * V * 12; cleared by the call
+ * Identical calls give identical bytes in every output, and the host port gives the device's bytes.
+ *
+ * No allocation, no host synchronisation.  A NULL required pointer (all but err and code), B, H, W or V below 1, V above
+ * BBD_GEO_MAX_VIEWS or scratch_words below the formula return BBD_E_BADARG; H * W > 2^23 or V * B * H * W > INT_MAX return
+ * BBD_E_TOOMANY.  Nothing is launched or written then. */
+#define BBD_GEO_MAX_VIEWS 8
+#define BBD_GEO_RUN 2048
+int bbd_geo_fwd(const float* q_tgt, const float* q_src, const float* T, const float* K, const float* inv_K,
+                double* pair_sum, int64_t* pair_count, float* err, uint8_t* code, int64_t* scratch, long scratch_words,
+                int B, int H, int W, int V, void* stream);
+int bbd_geo_bwd(const float* q_tgt, const float* q_src, const float* T, const float* K, const float* inv_K,
+                const double* g, float* grad_q_tgt, float* grad_q_src, float* grad_T, int64_t* scratch,
+                long scratch_words, int B, int H, int W, int V, void* stream);
 
 /* ---- Views (csrc/bbd_view.hip, pointcloud.Canvas): points and polylines rasterised into a z-buffered
  * canvas, resolved to RGB bytes.  The canvas is the caller's:
