@@ -25,6 +25,8 @@ globals().update(CONSTANTS)
 TRAJ_MODES = {mode.lower(): CONSTANTS["TRAJ_" + mode] for mode in ("SIM3", "SE3", "SCALE", "NONE")}
 # the host-side queries of bbd_conv3x3_wgrad have a header of their own (include/bbd_wgrad.h says why), read the same way
 WGRAD_HELPERS, _ = _abi.read_header(os.path.join(os.path.dirname(_abi.HEADER), "bbd_wgrad.h"))
+# ... and so have those of bbd_up2conv3x3_fwd / _bwd (include/bbd_up2conv.h)
+UP2CONV_HELPERS, _ = _abi.read_header(os.path.join(os.path.dirname(_abi.HEADER), "bbd_up2conv.h"))
 
 
 class HipLibrary:
@@ -44,7 +46,7 @@ class HipLibrary:
                 # the host-side helpers, under their ABI name minus `bbd_`: lib.num_tiles(H, W), lib.map_state_bytes(T);
                 # one without parameters is a constant of the build and is bound as its value: lib.tile_w, lib.smooth_chunks
                 setattr(self, name[len("bbd_"):], fn if proto.params else fn())
-        for name, proto in WGRAD_HELPERS.items():
+        for name, proto in list(WGRAD_HELPERS.items()) + list(UP2CONV_HELPERS.items()):
             fn = getattr(self._dll, name)
             fn.argtypes, fn.restype = [ctype for ctype, _ in proto.params], proto.restype
             setattr(self, name[len("bbd_"):], fn)

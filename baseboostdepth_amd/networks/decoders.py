@@ -66,7 +66,11 @@ class DepthDecoder(nn.Module):
                 x = first(x)
             xp = None
             if glued:
-                z = second.conv_raw(ops.upcat_pad_act(z, first.conv.conv.bias, skip))
+                if skip is None and ops.up2_conv3x3_routed(z, first.conv.conv.bias, second.conv.conv.weight):
+                    # up-sample + border + convolution as four 2x2 convolutions of z: no up-sampled copy
+                    z = ops.up2_conv3x3(z, first.conv.conv.bias, second.conv.conv.weight)
+                else:
+                    z = second.conv_raw(ops.upcat_pad_act(z, first.conv.conv.bias, skip))
                 if level > 0 and self._glue_level(level - 1, z) and ops.bias_elu_pad_supported(z, second.conv.conv.bias):
                     x, xp = ops.bias_elu_pad(z, second.conv.conv.bias)
                 else:

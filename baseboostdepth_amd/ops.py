@@ -1744,6 +1744,96 @@ def conv3x3_valid(xp, w, backend=None):
     return _Conv3x3Valid.apply(xp, w, backend or default_backend())
 
 
+# ---------------------------------------------------------------------------- up-sample + pad + 3x3 conv, sub-pixel form
+# 0: the finest decoder level keeps upcat_pad_act + convolution, as before (A/B runs)
+FUSED_UP2CONV = os.environ.get("BBD_FUSED_UP2CONV", "1") != "0"
+
+# (C, K, h, w) - channels in and out, size of the low-resolution map - of a decoder level without a skip connection whose
+# second ConvBlock `bbd_up2conv3x3_*` takes, at any batch size.  A row is here because tools/up2conv_bench.py measured the
+# new call's slowest repeat faster than the composition's fastest at batch 12, forward and full backward each
+# (profiles/decoder_up2conv/up2conv_bench.json); every other shape keeps the composition.
+UP2CONV_ROUTES = {
+    (16, 16, 96, 320),      # DepthDecoder upconv(0,1) at 640 x 192
+}
+
+
+def up2_conv3x3_shape(z, bias, weight):
+    """(N, C, K, h, w) of `bbd_up2conv3x3_*` for the convolution output `z`, its bias and the next 3x3 weight, or None
+    where the calls do not take them: contiguous fp32 GPU tensors, a [K,C,3,3] weight."""
+    if bias is None or not (z.dim() == 4 and weight.dim() == 4 and _glue_tensor(z) and _glue_tensor(bias) and _glue_tensor(weight)):
+        return None
+    N, C, h, w = z.shape
+    if weight.shape != (weight.shape[0], C, 3, 3) or bias.shape != (C,) or min(N, h, w) < 1:
+        return None
+    return N, C, weight.shape[0], h, w
+
+
+def up2_conv3x3_routed(z, bias, weight, backend=None):
+    """Does `conv2d(upcat_pad_act(z, bias), weight)` go to `bbd_up2conv3x3_*`?  Only for the measured rows of
+    UP2CONV_ROUTES, and never with BBD_FUSED_UP2CONV=0, BBD_FUSED_NN=0 or BBD_FUSED_DECODER_GLUE=0."""
+    if not (FUSED_UP2CONV and FUSED_NN and FUSED_DECODER_GLUE):
+        return False
+    shape = up2_conv3x3_shape(z, bias, weight)
+    if shape is None or shape[1:] not in UP2CONV_ROUTES:
+        return False
+    return bool((backend or default_backend()).lib.up2conv3x3_supported(*shape))
+
+
+def _weight_grad_of_padded(xp, weight, grad_out, backend):
+    """The weight gradient of `conv2d(xp, weight)` as today's composition computes it: `bbd_conv3x3_wgrad` for a routed
+    shape, MIOpen otherwise."""
+    if conv3x3_wgrad_routed(xp, weight, backend):
+        return conv3x3_wgrad(xp, grad_out, weight.shape[0], backend)
+    return torch.ops.aten.convolution_backward(grad_out, xp, weight, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
+                                               [False, True, False])[1]
+
+
+class _Up2Conv3x3(torch.autograd.Function):
+    """`F.conv2d(upcat_pad_act(z, bias, None), weight)` without the up-sampled, padded copy (csrc/bbd_up2conv.hip).  The
+    weight gradient is the composition's, bit for bit: the backward writes the copy into a transient buffer for it."""
+
+    @staticmethod
+    def forward(ctx, z, bias, weight, backend):
+        backend._check(z, bias, weight)
+        z, bias, weight = z.contiguous(), bias.contiguous(), weight.contiguous()
+        N, C, h, w = z.shape
+        K = weight.shape[0]
+        if not backend.lib.up2conv3x3_supported(N, C, K, h, w):
+            raise _lib.BbdError("bbd_up2conv3x3 does not take N=%d C=%d K=%d h=%d w=%d" % (N, C, K, h, w))
+        out = torch.empty(N, K, 2 * h, 2 * w, device=z.device, dtype=torch.float32)
+        backend.run("bbd_up2conv3x3_fwd", z, ptr(z), ptr(bias), ptr(weight), ptr(out), N, C, K, h, w)
+        ctx.save_for_backward(z, bias, weight)
+        ctx.backend = backend
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        z, bias, weight = ctx.saved_tensors
+        backend = ctx.backend
+        N, C, h, w = z.shape
+        K = weight.shape[0]
+        grad_out = grad_out.contiguous()
+        grad_z = grad_bias = grad_w = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            grad_z = torch.empty_like(z)
+            grad_bias = torch.empty(C, device=z.device, dtype=torch.float32)
+            n = backend.lib.up2conv3x3_scratch_doubles(N, C, K, h, w)
+            scratch = torch.empty(n, device=z.device, dtype=torch.float64)
+            backend.run("bbd_up2conv3x3_bwd", grad_out, ptr(grad_out), ptr(z), ptr(bias), ptr(weight), ptr(grad_z), ptr(grad_bias),
+                        ptr(scratch), n, N, C, K, h, w)
+        if ctx.needs_input_grad[2]:
+            xp = torch.empty(N, C, 2 * h + 2, 2 * w + 2, device=z.device, dtype=torch.float32)
+            backend.run("bbd_upcat_pad_act_fwd", z, ptr(z), ptr(bias), ptr(None), ptr(xp), N, C, 0, h, w)
+            grad_w = _weight_grad_of_padded(xp, weight, grad_out, backend)
+        return (grad_z if ctx.needs_input_grad[0] else None, grad_bias if ctx.needs_input_grad[1] else None, grad_w, None)
+
+
+def up2_conv3x3(z, bias, weight, backend=None):
+    """conv3x3(ReflectionPad2d(1)(nearest_x2(ELU(z + bias))), weight), bias-free: what `ConvBlock.conv_raw(upcat_pad_act(z,
+    bias))` returns, in sub-pixel form."""
+    return _Up2Conv3x3.apply(z, bias, weight, backend or default_backend())
+
+
 # ---------------------------------------------------------------------------- disparity head Conv3x3(C -> 1)
 class _DispConv(torch.autograd.Function):
     @staticmethod

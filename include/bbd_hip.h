@@ -58,8 +58,9 @@ extern "C" {
  * 22 = bbd_upcat_pad_act_* / bbd_bias_elu_pad_* (the depth decoder's bias + ELU inside its pad / up-sample passes);
  * 23 = bbd_post_process_uncert / bbd_sparsification (depth uncertainty from the flip pass and its AUSE / AURG scores);
  * 24 = bbd_conv3x3_wgrad (the decoder's 3x3 weight gradients from the NCHW tensors);
- * 25 = bbd_geo_fwd / bbd_geo_bwd (the geometry-consistency loss for training, forward and backward). */
-#define BBD_ABI_VERSION 25
+ * 25 = bbd_geo_fwd / bbd_geo_bwd (the geometry-consistency loss for training, forward and backward);
+ * 26 = bbd_up2conv3x3_fwd / _bwd (the decoder's finest up-sample + pad + 3x3 convolution in sub-pixel form). */
+#define BBD_ABI_VERSION 26
 
 /* Source frames live in separate tensors, one per frame id (inputs[("color", f, 0)],
  * trainer.py:428).  A "slot" indexes a host array of their base pointers. */
@@ -1126,6 +1127,36 @@ int bbd_bias_elu_pad_bwd(const float* grad_yp, const float* grad_y, const float*
 #define BBD_WGRAD_RUN 128
 int bbd_conv3x3_wgrad(const float* xp, const float* grad_z, float* grad_w, double* scratch, int N, int C, int K, int H,
                       int W, void* stream);
+
+/* Nearest x2 up-sampling, ReflectionPad2d(1) and a 3x3 convolution of ELU(z + bias) without the up-sampled copy
+ * (DepthDecoder upconv(0,1), the level without a skip connection).  All tensors contiguous fp32 NCHW:
+ *   bbd_up2conv3x3_fwd : out [N, K, 2h, 2w] = conv3x3(ReflectionPad2d(1)(nearest_x2(ELU(z + bias))), w), no bias added;
+ *                        z [N, C, h, w_] is the bias-free output of the convolution before and is left as it is, bias [C],
+ *                        w [K, C, 3, 3].  Output pixel (2i + a, 2j + b) reads kernel row r at source row
+ *                        i + floor((a + r - 1) / 2), clamped to the map (the reflection border of the up-sampled map is a
+ *                        clamp on the source); taps on one source pixel add their weights, so each parity is a 2x2
+ *                        convolution: 4/9 of the products.
+ *   bbd_up2conv3x3_bwd : grad_z [N, C, h, w_] = the adjoint of that applied to grad_out [N, K, 2h, 2w], times ELU'
+ *                        recomputed from z + bias; grad_bias [C] = sum grad_z from float64 per-workgroup partials that a
+ *                        second launch adds in a fixed order (scratch holds bbd_up2conv3x3_scratch_doubles(N, C, K, h, w_)
+ *                        doubles and scratch_doubles says how many it has; none is read before the call wrote it).
+ * Numerics: v_mfma_f32_16x16x4_f32 is an exact fp32 fma chain; no atomics, so two calls give equal bits, and every
+ * element of every output is written.  Forward: the longest chain is 4 taps x 16 channels = 64 fused multiply-adds (64
+ * roundings); each summed weight is added in double and rounded once (1); the input is ELU(z + bias): one rounding of
+ * the sum and expm1f's 2 ulp (3).  With 4 more for second-order terms that is BBD_UP2CONV_ROUNDINGS = 72:
+ *   |out - exact| <= BBD_UP2CONV_ROUNDINGS * 2^-24 * sum |w| |ELU(z + bias)|  element by element
+ * (nine separate taps would take 144 + 8).  Backward: kernel rows are summed as weights, kernel columns as data (two or
+ * three gradients added in fp32 before the product), at most 60 fused multiply-adds per element against the 576 products
+ * of the composition.
+ * The two host-side queries are declared in include/bbd_up2conv.h.  A shape bbd_up2conv3x3_supported refuses - anything
+ * but C = K = 16, N, h or w_ below 1, an output of 2^31 elements or more - a NULL pointer or a scratch that is too small
+ * return BBD_E_BADARG and launch nothing. */
+#define BBD_UP2CONV_ROUNDINGS 72
+int bbd_up2conv3x3_fwd(const float* z, const float* bias, const float* w, float* out, int N, int C, int K, int h, int w_,
+                       void* stream);
+int bbd_up2conv3x3_bwd(const float* grad_out, const float* z, const float* bias, const float* w, float* grad_z,
+                       float* grad_bias, double* scratch, int scratch_doubles, int N, int C, int K, int h, int w_,
+                       void* stream);
 
 /* ---- MonoViT encoder (BASELINE configs[4]): depth-wise convolution on token-layout activations ----------
  * The position encodings of the reference's MPViT (networksvit/mpvit.py:240-330: ConvPosEnc, ConvRelPosEnc)
