@@ -180,6 +180,68 @@ class GeometryConsistency(nn.Module):
         return ops.geometry_consistency(q_tgt, q_src, T, K, inv_K, want_err, want_code, backend)
 
 
+class DepthHints(nn.Module):
+    """Depth Hints (Watson et al., ICCV 2019) with the proxy depth computed inside the step: a semi-global
+    matcher (`ops.stereo_hints`) on the frame and its stereo partner gives a hint depth per pixel; wherever the stereo
+    partner warped with the HINT reprojects better than the step's own minimum photometric loss, the network's depth is
+    pulled towards the hint with log(1 + |depth - hint|).
+
+    `forward(left, right, K, inv_K, stereo_T, disps, to_optimise)`: `left`, `right` float32 [B,3,H,W]; `disps` the
+    sigmoid disparities of the scales (any resolution, up-sampled bilinearly as the reprojection does); `to_optimise`
+    one [B,H,W] map per scale.  Returns (term, share): the mean over scales of mean(mask * log(1 + |depth_s - hint|)) over
+    ALL pixels, and the mean of the masks.  Hint, its loss `l_h` (computed once) and the masks are made under no_grad:
+    gradients reach `disps` only.  The matcher's scratch is allocated on the first call and kept."""
+
+    def __init__(self, min_depth, max_depth, disparities=128, no_ssim=False):
+        super().__init__()
+        self.min_depth, self.max_depth = float(min_depth), float(max_depth)
+        self.disparities, self.no_ssim = int(disparities), bool(no_ssim)
+        self._scratch = None
+
+    def scratch(self, B, H, W, device):
+        need = ops.sgm_scratch_bytes(B, H, W, self.disparities, 8)
+        if self._scratch is None or self._scratch.numel() < need or self._scratch.device != device:
+            self._scratch = torch.empty(need, dtype=torch.uint8, device=device)
+        return self._scratch
+
+    @torch.no_grad()
+    def hints(self, left, right, K, inv_K, stereo_T, backend=None):
+        """(hint depth [B,H,W], valid [B,H,W], l_h [B,H,W]: the photometric loss of `right` warped with the hint)."""
+        B, _, H, W = left.shape
+        side = (stereo_T[:, 0, 3] > 0).to(torch.int32)
+        disp16, _ = ops.stereo_hints(left, right, side, self.disparities, scratch=self.scratch(B, H, W, left.device),
+                                     backend=backend)
+        hint, valid = ops.hint_depth(disp16, K, stereo_T)
+        depth = torch.where(valid, hint, torch.ones_like(hint)).unsqueeze(1)
+        points = ops.backproject(depth, inv_K, H, W, backend)
+        grid = ops.project3d(points, K, stereo_T, H, W, backend=backend)
+        warped = torch.nn.functional.grid_sample(right, grid, padding_mode="border", align_corners=True)
+        l_h = torch.abs(left - warped).mean(1)
+        if not self.no_ssim:
+            l_h = 0.85 * ops.ssim_map(warped, left, backend).mean(1) + 0.15 * l_h
+        return hint, valid, l_h
+
+    def forward(self, left, right, K, inv_K, stereo_T, disps, to_optimise, backend=None):
+        disps, to_optimise = list(disps), list(to_optimise)
+        if not disps or len(disps) != len(to_optimise):
+            raise ValueError("DepthHints: one minimum-loss map per disparity scale is needed, got %d and %d"
+                             % (len(disps), len(to_optimise)))
+        if right.shape != left.shape:
+            raise ValueError("DepthHints needs the stereo partner of every sample of the batch, got %s for %s"
+                             % (tuple(right.shape), tuple(left.shape)))
+        H, W = left.shape[2:]
+        hint, valid, l_h = self.hints(left, right, K, inv_K, stereo_T, backend)
+        term, share = 0.0, 0.0
+        for disp, best in zip(disps, to_optimise):
+            if tuple(disp.shape[2:]) != (H, W):
+                disp = torch.nn.functional.interpolate(disp, [H, W], mode="bilinear", align_corners=False)
+            depth = disp_to_depth(disp, self.min_depth, self.max_depth)[1][:, 0]
+            mask = valid & (l_h < best.detach())
+            term = term + torch.where(mask, torch.log1p(torch.abs(depth - hint)), torch.zeros_like(depth)).mean()
+            share = share + mask.to(torch.float32).mean()
+        return term / len(disps), share / len(disps)
+
+
 class Project3D(nn.Module):
     """points [n,4,H*W], K, T [n,4,4] -> sampling grid [n,H,W,2] in [-1,1]  (layers.py:170-195);
     differentiable w.r.t. points, T and K."""

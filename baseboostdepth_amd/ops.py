@@ -2542,6 +2542,76 @@ def geometry_consistency(q_tgt, q_src, T, K, inv_K, want_err=False, want_code=Fa
     return GeometryConsistency(loss, pair_sum, pair_count, err, code)
 
 
+# ---------------------------------------------------------------------------- depth hints (semi-global stereo matching)
+def sgm_scratch_bytes(B, H, W, D=128, paths=8):
+    """Bytes of scratch of bbd_sgm_hints: the formula of include/bbd_sgm.h (`lib.sgm_scratch_bytes`)."""
+    P = B * H * W
+    return (2 * P + 7) // 8 * 8 + 16 * P + 3 * P * D + (4 * P + 7) // 8 * 8
+
+
+def stereo_hints(left, right, side, disparities=128, paths=8, p1=_lib.SGM_P1, p2=_lib.SGM_P2,
+                 uniqueness=_lib.SGM_UNIQUENESS, fill=False, scratch=None, backend=None):
+    """Semi-global stereo matching of a rectified pair on the device (bbd_sgm_hints): `left`, `right`
+    float32 [B,3,H,W] in [0,1] (the frame and its stereo partner), `side` int32 [B] (0 = the partner lies to the right,
+    matches at x - d: `stereo_T[b,0,3] < 0`; otherwise mirrored, matches at x + d).  `disparities` 64, 128, 192 or 256,
+    `paths` 4 or 8, penalties 1 <= p1 < p2 <= 8129, `uniqueness` OpenCV's ratio in percent (0 = off), `fill` spreads the
+    nearest valid value along each row.  `scratch`: a uint8 tensor of at least `sgm_scratch_bytes(...)` bytes that the
+    caller keeps (allocated here when None).  Returns (disp16 int16 [B,H,W]: 16 x disparity, -16 = invalid; valid_count
+    int64 [B]).  Integer arithmetic: identical calls give identical bytes.  No host synchronisation, capturable."""
+    backend = backend or default_backend()
+    who = "stereo_hints: "
+    if not torch.is_tensor(left) or left.dtype != torch.float32 or left.dim() != 4 or left.shape[1] != 3 or left.numel() == 0:
+        raise ValueError(who + "left must be a non-empty float32 [B,3,H,W], got %s %s"
+                         % (getattr(left, "dtype", type(left)), tuple(getattr(left, "shape", ()))))
+    B, _, H, W = left.shape
+    if not torch.is_tensor(right) or right.dtype != torch.float32 or right.shape != left.shape:
+        raise ValueError(who + "right must be float32 %s like left, got %s %s"
+                         % (tuple(left.shape), getattr(right, "dtype", type(right)), tuple(getattr(right, "shape", ()))))
+    if not torch.is_tensor(side) or side.dtype != torch.int32 or tuple(side.shape) != (B,):
+        raise ValueError(who + "side must be int32 [%d], got %s %s"
+                         % (B, getattr(side, "dtype", type(side)), tuple(getattr(side, "shape", ()))))
+    D, paths, p1, p2, uniqueness = int(disparities), int(paths), int(p1), int(p2), int(uniqueness)
+    if D not in (64, 128, 192, 256) or paths not in (4, 8):
+        raise ValueError(who + "disparities must be 64, 128, 192 or 256 and paths 4 or 8, got %d and %d" % (D, paths))
+    if not 1 <= p1 < p2 <= _lib.SGM_MAX_P2:
+        raise ValueError(who + "the penalties must satisfy 1 <= p1 < p2 <= %d (8 paths of 62 + p2 must fit 16 bits), got "
+                         "%d and %d" % (_lib.SGM_MAX_P2, p1, p2))
+    if not 0 <= uniqueness <= 99:
+        raise ValueError(who + "uniqueness is a percentage in 0 .. 99, got %d" % uniqueness)
+    if B > 65535 or B * H * W > 1 << 26:
+        raise ValueError(who + "%d images of %d x %d pixels are more than one call holds" % (B, H, W))
+    need = sgm_scratch_bytes(B, H, W, D, paths)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=left.device)
+    elif not torch.is_tensor(scratch) or scratch.dtype != torch.uint8 or scratch.dim() != 1 or scratch.numel() < need \
+            or not scratch.is_contiguous() or scratch.data_ptr() % 8:
+        raise ValueError(who + "scratch must be a contiguous, 8-byte aligned uint8 tensor of at least %d bytes" % need)
+    for t, what in ((right, "right"), (side, "side"), (scratch, "scratch")):
+        if t.device != left.device:
+            raise ValueError(who + "%s is on %s, left on %s" % (what, t.device, left.device))
+    left, right, side = left.detach().contiguous(), right.detach().contiguous(), side.contiguous()
+    backend._check(left, right, side, scratch)
+    disp16 = torch.empty(B, H, W, dtype=torch.int16, device=left.device)
+    valid_count = torch.empty(B, dtype=torch.int64, device=left.device)
+    backend.run("bbd_sgm_hints", left, ptr(left), ptr(right), ptr(side), ptr(disp16), ptr(valid_count), ptr(scratch),
+                scratch.numel(), B, H, W, D, paths, p1, p2, uniqueness, int(bool(fill)))
+    return disp16, valid_count
+
+
+def hint_depth(disp16, K, stereo_T):
+    """`stereo_hints` disparities -> (depth float32 [B,H,W], valid bool [B,H,W]) in the units of the depth network's
+    `disp_to_depth` output: depth = fx * |t_x| / (disp16 / 16) with fx = K[b,0,0] in pixels and t_x = stereo_T[b,0,3] (0.1
+    for every KITTI pair of the loader).  A pixel is valid where disp16 > 0 (an invalid pixel is -16, and a disparity of
+    0 has no finite depth); the depth is 0 where it is not.  Plain torch, not a hot path."""
+    if disp16.dtype != torch.int16 or disp16.dim() != 3:
+        raise ValueError("hint_depth: disp16 must be int16 [B,H,W], got %s %s" % (disp16.dtype, tuple(disp16.shape)))
+    B = disp16.shape[0]
+    scale = (K.reshape(B, -1)[:, 0] * stereo_T.reshape(B, 16)[:, 3].abs()).to(torch.float32).view(B, 1, 1)
+    valid = disp16 > 0
+    d = disp16.to(torch.float32) / 16.0
+    return torch.where(valid, scale / torch.where(valid, d, torch.ones_like(d)), torch.zeros_like(d)), valid
+
+
 # ---------------------------------------------------------------------------- views (rasterised points and polylines)
 ViewState = collections.namedtuple("ViewState", "cells counters H W")
 ViewState.__doc__ = """The caller-owned canvas of the `bbd_view_*` entries: `cells` int64 [H,W] (the uint64 keys, empty =

@@ -66,6 +66,11 @@ _FLAGS = [
     # the depth of a frame and the depth of its temporal neighbours agree under the predicted motion.  0 = off: the step is
     # the step it was.  Nothing has been trained with it here: no value is recommended
     ("--geometry_consistency", dict(type=float, default=0.0, metavar="W")),
+    # Depth Hints (Watson et al., ICCV 2019): the weight of the log-L1 term that pulls the depth towards a
+    # proxy depth from semi-global stereo matching, computed on the device inside the step, wherever the proxy reprojects
+    # better than the step's own minimum loss; --hint_disparities is the matcher's search range (64, 128, 192 or 256).
+    # 0 = off: the step is the step it was.  Nothing has been trained with it here: no value is recommended
+    ("--depth_hints", dict(type=float, default=0.0, metavar="W")), ("--hint_disparities", dict(type=int, default=128)),
     # evaluate_depth.py: write the clouds of the first --cloud_count images of the split, prediction and ground truth, as
     # <index>_pred.ply / <index>_gt.ply into this directory while the batch is in HBM
     ("--save_clouds", dict(type=str, default=None, metavar="DIR")), ("--cloud_count", dict(type=int, default=8)),
@@ -133,6 +138,22 @@ def geometry_consistency_conflict(opt):
     if W > 0.0 and (getattr(opt, "rand", False) or getattr(opt, "trimin", False)):
         return ("--geometry_consistency needs one frame set for the whole batch: with --rand or --trimin the frame sets vary "
                 "per sample and the step runs in pooled form, where the term is not routed")
+    return None
+
+
+def depth_hints_conflict(opt):
+    """One sentence on why the depth-hint weight cannot be honoured, or None."""
+    W = getattr(opt, "depth_hints", 0.0)
+    if not W >= 0.0:
+        return "--depth_hints is the weight of a loss term and must not be negative, got %r" % (W,)
+    D = getattr(opt, "hint_disparities", 128)
+    if D not in (64, 128, 192, 256):
+        return "--hint_disparities must be 64, 128, 192 or 256, got %r" % (D,)
+    if W > 0.0 and (getattr(opt, "rand", False) or getattr(opt, "trimin", False)):
+        return ("--depth_hints needs the stereo partner of every sample of the batch: with --rand or --trimin the frame sets "
+                "vary per sample and the step runs in pooled form, where the term is not routed")
+    if W > 0.0 and getattr(opt, "ViT", False):
+        return "--depth_hints is not routed through the --ViT step"
     return None
 
 
@@ -222,6 +243,9 @@ class MonodepthOptions:
         if conflict:
             self.parser.error(conflict)
         conflict = geometry_consistency_conflict(self.options)
+        if conflict:
+            self.parser.error(conflict)
+        conflict = depth_hints_conflict(self.options)
         if conflict:
             self.parser.error(conflict)
         if self.options.rand and not self.options.no_step_graph:

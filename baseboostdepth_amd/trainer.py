@@ -17,7 +17,7 @@ import torch
 import torch.optim as optim
 
 from . import networks, ops, steptables
-from .layers import (SSIM, BackprojectDepth, GeometryConsistency, Project3D, disp_to_depth,
+from .layers import (SSIM, BackprojectDepth, DepthHints, GeometryConsistency, Project3D, disp_to_depth,
                      transformation_from_parameters)
 from .plan import STEREO, canonical_permutation, get_plan, owners_of, sample_max_offsets
 
@@ -132,6 +132,14 @@ class Trainer:
             if conflict:
                 raise ValueError(conflict)
             self.geometry_consistency = GeometryConsistency(opt.min_depth, opt.max_depth)
+        self.hint_weight = float(getattr(opt, "depth_hints", 0.0) or 0.0)
+        if self.hint_weight > 0.0:
+            from .options import depth_hints_conflict
+            conflict = depth_hints_conflict(opt)
+            if conflict:
+                raise ValueError(conflict)
+            self.depth_hints = DepthHints(opt.min_depth, opt.max_depth, getattr(opt, "hint_disparities", 128),
+                                          getattr(opt, "no_ssim", False))
         self.ssim = SSIM()
         self.backproject_depth = {0: BackprojectDepth(opt.batch_size, opt.height, opt.width)}
         self.project_3d = {0: Project3D(opt.batch_size, opt.height, opt.width)}
@@ -743,6 +751,8 @@ class Trainer:
             losses = self.compute_losses(inputs, outputs)
             if getattr(self, "geometry_weight", 0.0) > 0.0:
                 self.add_geometry_loss(inputs, outputs, losses)
+            if getattr(self, "hint_weight", 0.0) > 0.0:
+                self.add_hint_loss(inputs, outputs, losses)
         else:
             outputs = {}
             feats = self.models["encoder"](inputs["color", 0, 0])
@@ -1096,6 +1106,30 @@ class Trainer:
                                         backend=self._backend())
         losses["loss/geometry"] = res.loss.to(losses["loss"].dtype)
         losses["loss"] = losses["loss"] + self.geometry_weight * losses["loss/geometry"]
+
+    def add_hint_loss(self, inputs, outputs, losses):
+        """`--depth_hints W`: the Depth Hints term.  The matcher runs on `("color", 0, 0)` and the stereo
+        partner `("color", "s", 0)` of the batch that is already on the device; the hint's own photometric loss is compared
+        with `("bbd", "to_optimise")` of every scale.  Sets `losses["loss/hints"]` and `losses["hint_share"]` (the mean mask)
+        and adds W times the term to `losses["loss"]`; the gradient reaches the depth network only.  The photometric
+        gradient stays where the hint wins - the fused launches are frozen, the term is additive.  No host
+        synchronisation and one scratch kept by the layer, so the step still captures."""
+        from .options import depth_hints_conflict
+        opt = self.opt
+        conflict = depth_hints_conflict(opt)
+        if conflict or self.pooled_step:
+            raise ValueError(conflict or "--depth_hints is not routed through the pooled form of the step")
+        left, right = inputs[("color", 0, 0)], inputs.get(("color", STEREO, 0))
+        if right is None or right.shape != left.shape:
+            raise ValueError("--depth_hints needs the stereo partner of every sample of the batch, got %s for %d samples"
+                             % (None if right is None else tuple(right.shape), left.shape[0]))
+        best = outputs[("bbd", "to_optimise")]
+        term, share = self.depth_hints(left, right, inputs[("K", 0)], inputs[("inv_K", 0)], inputs["stereo_T"],
+                                       [outputs[("disp", s)] for s in opt.scales],
+                                       [best[i] for i in range(len(opt.scales))], backend=self._backend())
+        losses["loss/hints"] = term.to(losses["loss"].dtype)
+        losses["hint_share"] = share.detach()
+        losses["loss"] = losses["loss"] + self.hint_weight * losses["loss/hints"]
 
     def compute_losses(self, inputs, outputs):
         opt = self.opt

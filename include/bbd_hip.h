@@ -59,8 +59,9 @@ extern "C" {
  * 23 = bbd_post_process_uncert / bbd_sparsification (depth uncertainty from the flip pass and its AUSE / AURG scores);
  * 24 = bbd_conv3x3_wgrad (the decoder's 3x3 weight gradients from the NCHW tensors);
  * 25 = bbd_geo_fwd / bbd_geo_bwd (the geometry-consistency loss for training, forward and backward);
- * 26 = bbd_up2conv3x3_fwd / _bwd (the decoder's finest up-sample + pad + 3x3 convolution in sub-pixel form). */
-#define BBD_ABI_VERSION 26
+ * 26 = bbd_up2conv3x3_fwd / _bwd (the decoder's finest up-sample + pad + 3x3 convolution in sub-pixel form);
+ * 27 = bbd_sgm_hints (semi-global stereo matching: proxy disparities for --depth_hints). */
+#define BBD_ABI_VERSION 27
 
 /* Source frames live in separate tensors, one per frame id (inputs[("color", f, 0)],
  * trainer.py:428).  A "slot" indexes a host array of their base pointers. */
@@ -736,6 +737,39 @@ int bbd_geo_fwd(const float* q_tgt, const float* q_src, const float* T, const fl
 int bbd_geo_bwd(const float* q_tgt, const float* q_src, const float* T, const float* K, const float* inv_K,
                 const double* g, float* grad_q_tgt, float* grad_q_src, float* grad_T, int64_t* scratch,
                 long scratch_words, int B, int H, int W, int V, void* stream);
+
+/* ---- Semi-global stereo matching (csrc/bbd_sgm.hip, ops.stereo_hints, --depth_hints; Hirschmueller, PAMI
+ * 2008; Watson et al., ICCV 2019): a proxy disparity in 1/16 pixel for every pixel of a rectified pair.
+ *   left, right  float32 [B,3,H,W] in [0,1]: the frame and its stereo partner
+ *   side         int32 [B]: 0 = the partner lies to the right, matches at x - d; otherwise the roles are mirrored (the
+ *                frame is the right camera's, or the sample was flipped), matches at x + d.  A mirrored image is matched
+ *                through an index reflection of its loads and of its store: it gives the mirror image of what the
+ *                mirrored inputs give with side 0
+ *   disp16       OUT int16 [B,H,W]: 16 times the disparity, BBD_SGM_INVALID where the pixel failed a check
+ *   valid_count  OUT int64 [B]: the pixels that passed every check (before the fill): integer sums per workgroup and one
+ *                integer atomic add each, order-free
+ *   scratch      caller-owned, 8-byte aligned, at least bbd_sgm_scratch_bytes(B, H, W, D, paths) bytes
+ *                (include/bbd_sgm.h): grey bytes, census words, the cost volume as uint8, the path sums S as uint16 and
+ *                one selection word a pixel.  Need not be cleared
+ *   D            disparities 0 .. D - 1: 64, 128, 192 or 256;  paths  4 or 8
+ *   p1, p2       the penalties of the path recurrence, 1 <= p1 < p2 <= BBD_SGM_MAX_P2 (the bound that keeps 8 paths of
+ *                62 + p2 inside uint16); BBD_SGM_P1 / BBD_SGM_P2 are the defaults of the Python layer
+ *   uniqueness   OpenCV's uniquenessRatio in percent, 0 .. 99, 0 = no test;  fill  0 or 1: invalid pixels take the
+ *                nearest valid value of their row (smaller x first, in matching coordinates)
+ * The rules - grey, the 9 x 7 census, the Hamming cost, the recurrence, winner takes all with ties to the lowest d, the
+ * left-right check, the sub-pixel division - are csrc/bbd_sgm_math.h, shared with the host port.  Integer arithmetic:
+ * identical calls give identical bytes, and the host port gives the device's bytes.  No allocation, no host
+ * synchronisation.  A NULL pointer, a shape, D, paths, penalty, uniqueness or fill outside the above, a scratch that is
+ * misaligned or too small return BBD_E_BADARG; more than BBD_SGM_MAX_BATCH images or 2^26 pixels return BBD_E_TOOMANY.
+ * Nothing is launched or written then. */
+#define BBD_SGM_MAX_P2 8129
+#define BBD_SGM_P1 10
+#define BBD_SGM_P2 120
+#define BBD_SGM_UNIQUENESS 5
+#define BBD_SGM_INVALID (-16)
+int bbd_sgm_hints(const float* left, const float* right, const int32_t* side, int16_t* disp16, int64_t* valid_count,
+                  void* scratch, long scratch_bytes, int B, int H, int W, int D, int paths, int p1, int p2, int uniqueness,
+                  int fill, void* stream);
 
 /* ---- Views (csrc/bbd_view.hip, pointcloud.Canvas): points and polylines rasterised into a z-buffered
  * canvas, resolved to RGB bytes.  The canvas is the caller's:
