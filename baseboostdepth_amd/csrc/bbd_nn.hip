@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "../../include/bbd_hip.h"
+#include "bbd_bn_groups.h"
 
 namespace {
 
@@ -1584,22 +1585,6 @@ int bbd_bn_grouped_scratch_doubles(int max_group_rows, int G, int C, int HW) {
 }
 
 namespace {
-// copies the group table into the launch arguments; returns the largest group (0 = invalid table)
-int fill_groups(const int32_t* group_rows, int G, int N, BnArgs* a) {
-  if (!group_rows || G < 1 || G > BBD_BN_MAX_GROUPS || group_rows[0] != 0 || group_rows[G] != N) return 0;
-  int biggest = 0;
-  for (int g = 0; g < G; ++g) {
-    const int n = group_rows[g + 1] - group_rows[g];
-    if (n <= 0) return 0;
-    biggest = n > biggest ? n : biggest;
-  }
-  a->G = G;
-  for (int g = 0; g <= G; ++g) a->rows[g] = group_rows[g];
-  return biggest;
-}
-}  // namespace
-
-namespace {
 int launch_bn_fwd(BnArgs& a, int biggest, bool running, hipStream_t st) {
   a.split = pick_split(biggest, a.HW);
   if ((long long)biggest * a.HW <= BN_SMALL_ELEMS) {       // one launch (+ a C-thread one for the cross-group results)
@@ -1639,38 +1624,51 @@ void fill_bwd(BnArgs& a, const float* x, const float* y, const float* grad_y, co
   a.invstd = const_cast<float*>(save_invstd); a.dx = grad_x; a.dres = grad_residual; a.dgamma = grad_gamma;
   a.dbeta = grad_beta; a.part = scratch; a.N = N; a.C = C; a.HW = HW; a.relu = relu;
 }
+
+// The one body per direction behind every bbd_bn_act_* entry point: they differ in the description of the call groups only
+int bn_fwd(const float* x, const float* residual, const float* gamma, const float* beta, float* y, float* save_mean,
+           float* save_invstd, float* running_mean, float* running_var, long long* num_batches_tracked, double* scratch,
+           const BbdBnGroups& groups, int N, int C, int HW, double eps, double momentum, int relu, void* stream) {
+  if (!x || !gamma || !beta || !y || !save_mean || !save_invstd || !scratch || N <= 0 || C <= 0 || HW <= 0)
+    return BBD_E_BADARG;
+  if ((running_mean == nullptr) != (running_var == nullptr)) return BBD_E_BADARG;
+  BnArgs a = {};
+  const int biggest = bbd_bn_resolve_groups(groups, N, &a);
+  if (!biggest) return BBD_E_BADARG;
+  fill_fwd(a, x, residual, gamma, beta, y, save_mean, save_invstd, running_mean, running_var, num_batches_tracked, scratch,
+           N, C, HW, eps, momentum, relu);
+  return launch_bn_fwd(a, biggest, running_mean || num_batches_tracked, static_cast<hipStream_t>(stream));
+}
+
+int bn_bwd(const float* x, const float* y, const float* grad_y, const float* gamma, const float* beta,
+           const float* save_mean, const float* save_invstd, float* grad_x, float* grad_residual, float* grad_gamma,
+           float* grad_beta, double* scratch, const BbdBnGroups& groups, int N, int C, int HW, int relu, void* stream) {
+  if (!x || !grad_y || !gamma || !save_mean || !save_invstd || !grad_x || !grad_gamma || !grad_beta || !scratch ||
+      N <= 0 || C <= 0 || HW <= 0 || (relu && !y && !beta))
+    return BBD_E_BADARG;
+  BnArgs a = {};
+  const int biggest = bbd_bn_resolve_groups(groups, N, &a);
+  if (!biggest) return BBD_E_BADARG;
+  fill_bwd(a, x, y, grad_y, gamma, beta, save_mean, save_invstd, grad_x, grad_residual, grad_gamma, grad_beta, scratch, N, C,
+           HW, relu);
+  return launch_bn_bwd(a, biggest, static_cast<hipStream_t>(stream));
+}
 }  // namespace
 
 int bbd_bn_act_grouped_fwd(const float* x, const float* residual, const float* gamma, const float* beta, float* y,
                            float* save_mean, float* save_invstd, float* running_mean, float* running_var,
                            long long* num_batches_tracked, double* scratch, const int32_t* group_rows, int G,
                            int untracked_groups, int N, int C, int HW, double eps, double momentum, int relu, void* stream) {
-  if (!x || !gamma || !beta || !y || !save_mean || !save_invstd || !scratch || N <= 0 || C <= 0 || HW <= 0)
-    return BBD_E_BADARG;
-  if (untracked_groups < 0 || untracked_groups >= G) return BBD_E_BADARG;
-  if ((running_mean == nullptr) != (running_var == nullptr)) return BBD_E_BADARG;
-  BnArgs a = {};
-  const int biggest = fill_groups(group_rows, G, N, &a);
-  if (!biggest) return BBD_E_BADARG;
-  fill_fwd(a, x, residual, gamma, beta, y, save_mean, save_invstd, running_mean, running_var, num_batches_tracked, scratch,
-           N, C, HW, eps, momentum, relu);
-  a.untracked = untracked_groups;
-  return launch_bn_fwd(a, biggest, running_mean || num_batches_tracked, static_cast<hipStream_t>(stream));
+  return bn_fwd(x, residual, gamma, beta, y, save_mean, save_invstd, running_mean, running_var, num_batches_tracked, scratch,
+                {group_rows, nullptr, G, untracked_groups, 0}, N, C, HW, eps, momentum, relu, stream);
 }
 
 int bbd_bn_act_grouped_bwd(const float* x, const float* y, const float* grad_y, const float* gamma, const float* beta,
                            const float* save_mean, const float* save_invstd, float* grad_x, float* grad_residual,
                            float* grad_gamma, float* grad_beta, double* scratch, const int32_t* group_rows, int G, int N,
                            int C, int HW, int relu, void* stream) {
-  if (!x || !grad_y || !gamma || !save_mean || !save_invstd || !grad_x || !grad_gamma || !grad_beta || !scratch ||
-      N <= 0 || C <= 0 || HW <= 0 || (relu && !y && !beta))
-    return BBD_E_BADARG;
-  BnArgs a = {};
-  const int biggest = fill_groups(group_rows, G, N, &a);
-  if (!biggest) return BBD_E_BADARG;
-  fill_bwd(a, x, y, grad_y, gamma, beta, save_mean, save_invstd, grad_x, grad_residual, grad_gamma, grad_beta, scratch, N, C,
-           HW, relu);
-  return launch_bn_bwd(a, biggest, static_cast<hipStream_t>(stream));
+  return bn_bwd(x, y, grad_y, gamma, beta, save_mean, save_invstd, grad_x, grad_residual, grad_gamma, grad_beta, scratch,
+                {group_rows, nullptr, G, 0, 0}, N, C, HW, relu, stream);
 }
 
 // Device-resident group table (ABI 7): the same launches with NOTHING of the batch signature in their arguments.
@@ -1679,30 +1677,16 @@ int bbd_bn_act_grouped_dev_fwd(const float* x, const float* residual, const floa
                                long long* num_batches_tracked, double* scratch, const int32_t* group_table, int G,
                                int max_group_rows, int N, int C, int HW, double eps, double momentum, int relu,
                                void* stream) {
-  if (!x || !gamma || !beta || !y || !save_mean || !save_invstd || !scratch || !group_table || N <= 0 || C <= 0 || HW <= 0)
-    return BBD_E_BADARG;
-  if (G < 1 || G > BBD_BN_MAX_GROUPS || max_group_rows < 1 || max_group_rows > N) return BBD_E_BADARG;
-  if ((running_mean == nullptr) != (running_var == nullptr)) return BBD_E_BADARG;
-  BnArgs a = {};
-  fill_fwd(a, x, residual, gamma, beta, y, save_mean, save_invstd, running_mean, running_var, num_batches_tracked, scratch,
-           N, C, HW, eps, momentum, relu);
-  a.G = G; a.rows_dev = group_table;
-  return launch_bn_fwd(a, max_group_rows, running_mean || num_batches_tracked, static_cast<hipStream_t>(stream));
+  return bn_fwd(x, residual, gamma, beta, y, save_mean, save_invstd, running_mean, running_var, num_batches_tracked, scratch,
+                {nullptr, group_table, G, 0, max_group_rows}, N, C, HW, eps, momentum, relu, stream);
 }
 
 int bbd_bn_act_grouped_dev_bwd(const float* x, const float* y, const float* grad_y, const float* gamma, const float* beta,
                                const float* save_mean, const float* save_invstd, float* grad_x, float* grad_residual,
                                float* grad_gamma, float* grad_beta, double* scratch, const int32_t* group_table, int G,
                                int max_group_rows, int N, int C, int HW, int relu, void* stream) {
-  if (!x || !grad_y || !gamma || !save_mean || !save_invstd || !grad_x || !grad_gamma || !grad_beta || !scratch ||
-      !group_table || N <= 0 || C <= 0 || HW <= 0 || (relu && !y && !beta))
-    return BBD_E_BADARG;
-  if (G < 1 || G > BBD_BN_MAX_GROUPS || max_group_rows < 1 || max_group_rows > N) return BBD_E_BADARG;
-  BnArgs a = {};
-  fill_bwd(a, x, y, grad_y, gamma, beta, save_mean, save_invstd, grad_x, grad_residual, grad_gamma, grad_beta, scratch, N, C,
-           HW, relu);
-  a.G = G; a.rows_dev = group_table;
-  return launch_bn_bwd(a, max_group_rows, static_cast<hipStream_t>(stream));
+  return bn_bwd(x, y, grad_y, gamma, beta, save_mean, save_invstd, grad_x, grad_residual, grad_gamma, grad_beta, scratch,
+                {nullptr, group_table, G, 0, max_group_rows}, N, C, HW, relu, stream);
 }
 
 // ---- encoder stem: conv1 -> bn1 + ReLU -> MaxPool2d(3, 2, 1).  Only the two-launch form exists (BBD_STEM_MIN_ELEMS)
@@ -1762,68 +1746,66 @@ void fill_stem_bwd(BnArgs& a, const float* x, const float* grad_y, const float* 
   a.gpool = grad_pooled;
   a.code = const_cast<uint8_t*>(code);
 }
+
+int stem_fwd(const float* x, const float* gamma, const float* beta, float* y, float* pooled, uint8_t* code, float* save_mean,
+             float* save_invstd, float* running_mean, float* running_var, long long* num_batches_tracked, double* scratch,
+             const BbdBnGroups& groups, int N, int C, int H, int W, double eps, double momentum, void* stream) {
+  if (!stem_fwd_ptrs_ok(x, gamma, beta, y, pooled, code, save_mean, save_invstd, running_mean, running_var, scratch))
+    return BBD_E_BADARG;
+  BnArgs a = {};
+  const int biggest = bbd_bn_resolve_groups(groups, N, &a);
+  if (!biggest || !stem_shape_ok(biggest, N, C, H, W)) return BBD_E_BADARG;
+  fill_fwd(a, x, nullptr, gamma, beta, y, save_mean, save_invstd, running_mean, running_var, num_batches_tracked, scratch, N, C,
+           H * W, eps, momentum, 1);
+  a.pooled = pooled; a.code = code;
+  return launch_stem_fwd(a, biggest, H, W, static_cast<hipStream_t>(stream));
+}
+
+int stem_bwd(const float* x, const float* grad_y, const float* grad_pooled, const uint8_t* code, const float* gamma,
+             const float* beta, const float* save_mean, const float* save_invstd, float* grad_x, float* grad_gamma,
+             float* grad_beta, double* scratch, const BbdBnGroups& groups, int N, int C, int H, int W, void* stream) {
+  if (!stem_bwd_ptrs_ok(x, grad_y, grad_pooled, code, gamma, beta, save_mean, save_invstd, grad_x, grad_gamma, grad_beta,
+                        scratch))
+    return BBD_E_BADARG;
+  BnArgs a = {};
+  const int biggest = bbd_bn_resolve_groups(groups, N, &a);
+  if (!biggest || !stem_shape_ok(biggest, N, C, H, W)) return BBD_E_BADARG;
+  fill_stem_bwd(a, x, grad_y, grad_pooled, code, gamma, beta, save_mean, save_invstd, grad_x, grad_gamma, grad_beta, scratch,
+                N, C, H, W);
+  return launch_stem_bwd(a, biggest, W, static_cast<hipStream_t>(stream));
+}
 }  // namespace
 
 int bbd_stem_fwd(const float* x, const float* gamma, const float* beta, float* y, float* pooled, uint8_t* code,
                  float* save_mean, float* save_invstd, float* running_mean, float* running_var,
                  long long* num_batches_tracked, double* scratch, const int32_t* group_rows, int G, int untracked_groups,
                  int N, int C, int H, int W, double eps, double momentum, void* stream) {
-  if (!stem_fwd_ptrs_ok(x, gamma, beta, y, pooled, code, save_mean, save_invstd, running_mean, running_var, scratch))
-    return BBD_E_BADARG;
-  if (untracked_groups < 0 || untracked_groups >= G) return BBD_E_BADARG;
-  BnArgs a = {};
-  const int biggest = fill_groups(group_rows, G, N, &a);
-  if (!biggest || !stem_shape_ok(biggest, N, C, H, W)) return BBD_E_BADARG;
-  fill_fwd(a, x, nullptr, gamma, beta, y, save_mean, save_invstd, running_mean, running_var, num_batches_tracked, scratch, N, C,
-           H * W, eps, momentum, 1);
-  a.untracked = untracked_groups;
-  a.pooled = pooled; a.code = code;
-  return launch_stem_fwd(a, biggest, H, W, static_cast<hipStream_t>(stream));
+  return stem_fwd(x, gamma, beta, y, pooled, code, save_mean, save_invstd, running_mean, running_var, num_batches_tracked,
+                  scratch, {group_rows, nullptr, G, untracked_groups, 0}, N, C, H, W, eps, momentum, stream);
 }
 
 int bbd_stem_bwd(const float* x, const float* grad_y, const float* grad_pooled, const uint8_t* code, const float* gamma,
                  const float* beta, const float* save_mean, const float* save_invstd, float* grad_x, float* grad_gamma,
                  float* grad_beta, double* scratch, const int32_t* group_rows, int G, int N, int C, int H, int W,
                  void* stream) {
-  if (!stem_bwd_ptrs_ok(x, grad_y, grad_pooled, code, gamma, beta, save_mean, save_invstd, grad_x, grad_gamma, grad_beta,
-                        scratch))
-    return BBD_E_BADARG;
-  BnArgs a = {};
-  const int biggest = fill_groups(group_rows, G, N, &a);
-  if (!biggest || !stem_shape_ok(biggest, N, C, H, W)) return BBD_E_BADARG;
-  fill_stem_bwd(a, x, grad_y, grad_pooled, code, gamma, beta, save_mean, save_invstd, grad_x, grad_gamma, grad_beta, scratch,
-                N, C, H, W);
-  return launch_stem_bwd(a, biggest, W, static_cast<hipStream_t>(stream));
+  return stem_bwd(x, grad_y, grad_pooled, code, gamma, beta, save_mean, save_invstd, grad_x, grad_gamma, grad_beta, scratch,
+                  {group_rows, nullptr, G, 0, 0}, N, C, H, W, stream);
 }
 
 int bbd_stem_dev_fwd(const float* x, const float* gamma, const float* beta, float* y, float* pooled, uint8_t* code,
                      float* save_mean, float* save_invstd, float* running_mean, float* running_var,
                      long long* num_batches_tracked, double* scratch, const int32_t* group_table, int G,
                      int max_group_rows, int N, int C, int H, int W, double eps, double momentum, void* stream) {
-  if (!stem_fwd_ptrs_ok(x, gamma, beta, y, pooled, code, save_mean, save_invstd, running_mean, running_var, scratch))
-    return BBD_E_BADARG;
-  if (!group_table || G < 1 || G > BBD_BN_MAX_GROUPS || !stem_shape_ok(max_group_rows, N, C, H, W)) return BBD_E_BADARG;
-  BnArgs a = {};
-  fill_fwd(a, x, nullptr, gamma, beta, y, save_mean, save_invstd, running_mean, running_var, num_batches_tracked, scratch, N, C,
-           H * W, eps, momentum, 1);
-  a.G = G; a.rows_dev = group_table;
-  a.pooled = pooled; a.code = code;
-  return launch_stem_fwd(a, max_group_rows, H, W, static_cast<hipStream_t>(stream));
+  return stem_fwd(x, gamma, beta, y, pooled, code, save_mean, save_invstd, running_mean, running_var, num_batches_tracked,
+                  scratch, {nullptr, group_table, G, 0, max_group_rows}, N, C, H, W, eps, momentum, stream);
 }
 
 int bbd_stem_dev_bwd(const float* x, const float* grad_y, const float* grad_pooled, const uint8_t* code, const float* gamma,
                      const float* beta, const float* save_mean, const float* save_invstd, float* grad_x, float* grad_gamma,
                      float* grad_beta, double* scratch, const int32_t* group_table, int G, int max_group_rows, int N, int C,
                      int H, int W, void* stream) {
-  if (!stem_bwd_ptrs_ok(x, grad_y, grad_pooled, code, gamma, beta, save_mean, save_invstd, grad_x, grad_gamma, grad_beta,
-                        scratch))
-    return BBD_E_BADARG;
-  if (!group_table || G < 1 || G > BBD_BN_MAX_GROUPS || !stem_shape_ok(max_group_rows, N, C, H, W)) return BBD_E_BADARG;
-  BnArgs a = {};
-  fill_stem_bwd(a, x, grad_y, grad_pooled, code, gamma, beta, save_mean, save_invstd, grad_x, grad_gamma, grad_beta, scratch,
-                N, C, H, W);
-  a.G = G; a.rows_dev = group_table;
-  return launch_stem_bwd(a, max_group_rows, W, static_cast<hipStream_t>(stream));
+  return stem_bwd(x, grad_y, grad_pooled, code, gamma, beta, save_mean, save_invstd, grad_x, grad_gamma, grad_beta, scratch,
+                  {nullptr, group_table, G, 0, max_group_rows}, N, C, H, W, stream);
 }
 
 int bbd_bn_act_fwd(const float* x, const float* residual, const float* gamma, const float* beta, float* y,
@@ -1831,16 +1813,16 @@ int bbd_bn_act_fwd(const float* x, const float* residual, const float* gamma, co
                    long long* num_batches_tracked, double* scratch, int N, int C, int HW, double eps, double momentum,
                    int relu, void* stream) {
   const int32_t rows[2] = {0, N};
-  return bbd_bn_act_grouped_fwd(x, residual, gamma, beta, y, save_mean, save_invstd, running_mean, running_var,
-                                num_batches_tracked, scratch, rows, 1, 0, N, C, HW, eps, momentum, relu, stream);
+  return bn_fwd(x, residual, gamma, beta, y, save_mean, save_invstd, running_mean, running_var, num_batches_tracked, scratch,
+                {rows, nullptr, 1, 0, 0}, N, C, HW, eps, momentum, relu, stream);
 }
 
 int bbd_bn_act_bwd(const float* x, const float* y, const float* grad_y, const float* gamma, const float* beta,
                    const float* save_mean, const float* save_invstd, float* grad_x, float* grad_residual, float* grad_gamma, float* grad_beta,
                    double* scratch, int N, int C, int HW, int relu, void* stream) {
   const int32_t rows[2] = {0, N};
-  return bbd_bn_act_grouped_bwd(x, y, grad_y, gamma, beta, save_mean, save_invstd, grad_x, grad_residual, grad_gamma,
-                                grad_beta, scratch, rows, 1, N, C, HW, relu, stream);
+  return bn_bwd(x, y, grad_y, gamma, beta, save_mean, save_invstd, grad_x, grad_residual, grad_gamma, grad_beta, scratch,
+                {rows, nullptr, 1, 0, 0}, N, C, HW, relu, stream);
 }
 
 int bbd_reflect_pad1_fwd(const float* in, float* out, int planes, int H, int W, void* stream) {

@@ -29,8 +29,8 @@ class FusedBatchNorm2d(nn.BatchNorm2d):
                                       self.momentum, self.eps, relu, num_batches_tracked=self.num_batches_tracked)
         if self.training and x.is_cuda:
             from .. import ops
-            assert ops._bn_groups is None and ops._bn_device is None, \
-                "a batched pass with call groups needs the fused BatchNorm path"
+            if ops.call_groups(x.shape[0]).rows != (x.shape[0],):
+                raise RuntimeError("a batched pass with call groups needs the fused BatchNorm path")
         y = super().forward(x)
         if residual is not None:
             y = y + residual
@@ -157,7 +157,7 @@ class ResnetEncoder(nn.Module):
         if (isinstance(bn, FusedBatchNorm2d) and isinstance(e.maxpool, MaxPool3s2) and bn.fused and x.is_cuda and bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None
                 and x.dtype == torch.float32 and x.dim() == 4 and x.shape[0] * x.shape[1] <= 65535):
             from .. import ops
-            if ops.FUSED_NN and ops.FUSED_STEM and ops.stem_supported(x, ops._stem_rows(x.shape[0])):
+            if ops.FUSED_NN and ops.FUSED_STEM and ops.stem_supported(x, ops.call_groups(x.shape[0]).biggest):
                 return ops.stem_bn_relu_pool(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps,
                                              want_y=self.stem_feature, num_batches_tracked=bn.num_batches_tracked)
         f0 = bn(x, relu=True)

@@ -1202,60 +1202,86 @@ def residual_add(x, branch, mask, backend=None):
 
 # ---------------------------------------------------------------------------- BatchNorm (+add) (+ReLU)
 BN_MAX_GROUPS = _lib.BN_MAX_GROUPS
-_bn_groups = None           # row counts of the call groups of the batched pass being run (None = one group)
-_bn_untracked = 0           # trailing groups of it that are padding (no running-statistics update)
-_bn_device = None           # (device group table, G, largest group) of `bn_call_groups_device`, or None
+_call_groups = None         # the `CallGroups` of the batched pass being run (None = one group, the whole batch)
 
 
-class bn_call_groups:
-    """`with ops.bn_call_groups([n_0, n_1, ...]):` - every fused BatchNorm inside treats its batch as consecutive
-    call groups of n_g samples with their own batch statistics: one batched pass of a network computes what the
-    reference's separate calls on the sub-batches compute (the pose network: trainer.py:348-418)."""
+class CallGroups(collections.namedtuple("CallGroups", "rows untracked table groups bound")):
+    """The call groups of a fused BatchNorm: host row counts `rows` with `untracked` trailing padding groups, or a device
+    `table` of `groups` groups of at most `bound` rows each (the fields of the other description are None)."""
+    __slots__ = ()
+    G = property(lambda self: len(self.rows) if self.table is None else self.groups)
+    biggest = property(lambda self: max(self.rows) if self.table is None else self.bound)
+    infix = property(lambda self: "" if self.table is None else "_dev")          # bbd_bn_act_grouped<infix>_fwd, ...
 
-    def __init__(self, rows, padding_groups=0):
-        """`padding_groups`: the last that many groups are padding rows - normalised, but the running statistics and
-        num_batches_tracked see only the real calls (bbd_bn_act_grouped_fwd, `untracked_groups`)."""
-        self.rows = [int(r) for r in rows] if rows is not None and len(rows) > 1 else None
-        self.untracked = int(padding_groups) if self.rows is not None else 0
-        assert self.rows is None or (len(self.rows) <= BN_MAX_GROUPS and min(self.rows) > 0)
-        assert 0 <= self.untracked < max(len(self.rows or [0]), 1)
+    def fwd_args(self):
+        """What follows `scratch` in the forward entry points; `bwd_args`: in the backward ones."""
+        if self.table is not None:
+            return ptr(self.table), self.G, self.bound
+        return (ctypes.c_int32 * (self.G + 1))(*np.cumsum((0,) + self.rows).tolist()), self.G, self.untracked
+
+    def bwd_args(self):
+        return self.fwd_args()[:2 if self.table is None else 3]
+
+    def check(self, N=None):
+        """ValueError unless this describes a batch of N rows (None: only what does not depend on the batch)."""
+        host = self.table is None
+        if not (1 <= self.G <= BN_MAX_GROUPS and ((min(self.rows) > 0 and 0 <= self.untracked < self.G) if host else
+                                                  (self.table.dtype == torch.int32 and self.table.numel() >= BN_MAX_GROUPS + 2))):
+            raise ValueError("no description of 1 .. %d call groups: %s" % (BN_MAX_GROUPS, tuple(self)))
+        if N is not None and (sum(self.rows) != N if host else self.bound > N):
+            raise ValueError("ops.bn_call_groups does not describe this batch (%s vs %d rows)" % (self.rows or self.bound, N))
+        return self
+
+
+def call_groups(N):
+    """The active description of the call groups, or the single group of a batch of N rows."""
+    return _call_groups if _call_groups is not None else CallGroups((N,), 0, None, None, None)
+
+
+class _CallGroupsScope:
+    def __init__(self, groups):
+        self.groups = groups
 
     def __enter__(self):
-        global _bn_groups, _bn_untracked
-        self.prev, _bn_groups = (_bn_groups, _bn_untracked), self.rows
-        _bn_untracked = self.untracked
+        global _call_groups
+        if self.groups is not None and _call_groups is not None and self.groups.infix != _call_groups.infix:
+            raise ValueError("a host and a device description of the call groups are active together")
+        self.prev, _call_groups = _call_groups, self.groups
         return self
 
     def __exit__(self, *exc):
-        global _bn_groups, _bn_untracked
-        _bn_groups, _bn_untracked = self.prev
+        global _call_groups
+        _call_groups = self.prev
 
 
-class bn_call_groups_device:
+def bn_call_groups(rows, padding_groups=0):
+    """`with ops.bn_call_groups([n_0, n_1, ...]):` - every fused BatchNorm inside treats its batch as consecutive
+    call groups of n_g samples with their own batch statistics: one batched pass of a network computes what the
+    reference's separate calls on the sub-batches compute (the pose network: trainer.py:348-418).  `padding_groups`:
+    the last that many groups are padding rows - normalised, but the running statistics and num_batches_tracked see
+    only the real calls (bbd_bn_act_grouped_fwd, `untracked_groups`).  None or fewer than two groups: no groups."""
+    if rows is None or len(rows) <= 1:
+        return _CallGroupsScope(None)
+    return _CallGroupsScope(CallGroups(tuple(int(r) for r in rows), int(padding_groups), None, None, None).check())
+
+
+def bn_call_groups_device(table, groups, max_rows):
     """`with ops.bn_call_groups_device(table, G, max_rows):` - the call groups of `bn_call_groups`, read from a DEVICE table
     (int32 [BN_MAX_GROUPS + 2]: rows[0..G], number of tracked groups at index BN_MAX_GROUPS + 1; groups may be empty) by
     `bbd_bn_act_grouped_dev_*`: nothing of the batch signature is in the launch arguments, so one captured step graph
     serves every ordering with the same padded row count (`pooled.PooledStep`).  `max_rows` bounds every group."""
-
-    def __init__(self, table, groups, max_rows):
-        assert table.dtype == torch.int32 and table.numel() >= BN_MAX_GROUPS + 2 and 1 <= groups <= BN_MAX_GROUPS
-        self.spec = (table, int(groups), int(max_rows))
-
-    def __enter__(self):
-        global _bn_device
-        self.prev, _bn_device = _bn_device, self.spec
-        return self
-
-    def __exit__(self, *exc):
-        global _bn_device
-        _bn_device = self.prev
+    return _CallGroupsScope(CallGroups(None, None, table, int(groups), int(max_rows)).check())
 
 
-def _group_table(rows):
-    arr = (ctypes.c_int32 * (len(rows) + 1))()
-    for i, r in enumerate(rows):
-        arr[i + 1] = arr[i] + r
-    return arr
+def check_group_table(section, G, bound, R):
+    """ValueError unless the host copy of a packed group table (`bn_call_groups_device`'s layout) is one that launches with
+    a grid of G groups and scratch for groups of `bound` rows can take for a pass of R rows: the kernels trust the table."""
+    rows, tracked = [int(v) for v in section[:BN_MAX_GROUPS + 1]], int(section[BN_MAX_GROUPS + 1])
+    sizes = [b - a for a, b in zip(rows, rows[1:])]
+    if not (1 <= G <= BN_MAX_GROUPS and rows[0] == 0 and 0 <= min(sizes) and max(sizes) <= bound
+            and all(r == R for r in rows[G:]) and 0 <= tracked <= sum(n > 0 for n in sizes)):
+        raise ValueError("group table %s with %d tracked groups: not %d rows in at most %d groups of at most %d rows"
+                         % (rows, tracked, R, G, bound))
 
 
 class _BatchNormAct(torch.autograd.Function):
@@ -1271,60 +1297,34 @@ class _BatchNormAct(torch.autograd.Function):
             assert residual.shape == x.shape
         backend._check(x, weight, bias, residual, running_mean, running_var)
         y = torch.empty_like(x)
-        if _bn_device is not None:
-            # group table on the device: the launch arguments hold nothing of the batch signature
-            table, G, biggest = _bn_device
-            assert _bn_groups is None and biggest <= N
-            rows = (table, G, biggest)
-            mean = torch.empty(G, C, device=x.device, dtype=torch.float32)
-            invstd = torch.empty(G, C, device=x.device, dtype=torch.float32)
-            scratch = torch.empty(backend.lib.bn_grouped_scratch_doubles(biggest, G, C, H * W), device=x.device,
-                                  dtype=torch.float64)
-            backend.run("bbd_bn_act_grouped_dev_fwd", x, ptr(x), ptr(residual), ptr(weight), ptr(bias), ptr(y), ptr(mean),
-                        ptr(invstd), ptr(running_mean), ptr(running_var), ptr(batches), ptr(scratch), ptr(table), G,
-                        biggest, N, C, H * W, float(eps), float(momentum), int(relu))
-            ctx.save_for_backward(x, y if (relu and residual is not None) else None, weight, bias, mean, invstd)
-            ctx.meta = (bool(relu), residual is not None, backend, rows)
-            return y
-        rows = _bn_groups if _bn_groups is not None else [N]
-        assert sum(rows) == N, "ops.bn_call_groups does not describe this batch (%s vs %d rows)" % (rows, N)
-        G = len(rows)
-        mean = torch.empty(G, C, device=x.device, dtype=torch.float32)
-        invstd = torch.empty(G, C, device=x.device, dtype=torch.float32)
-        scratch = torch.empty(backend.lib.bn_grouped_scratch_doubles(max(rows), G, C, H * W), device=x.device,
+        groups = call_groups(N).check(N)
+        mean = torch.empty(groups.G, C, device=x.device, dtype=torch.float32)
+        invstd = torch.empty(groups.G, C, device=x.device, dtype=torch.float32)
+        scratch = torch.empty(backend.lib.bn_grouped_scratch_doubles(groups.biggest, groups.G, C, H * W), device=x.device,
                               dtype=torch.float64)
-        backend.run("bbd_bn_act_grouped_fwd", x, ptr(x), ptr(residual), ptr(weight), ptr(bias), ptr(y), ptr(mean),
-                    ptr(invstd), ptr(running_mean), ptr(running_var), ptr(batches), ptr(scratch), _group_table(rows), G,
-                    _bn_untracked if _bn_groups is not None else 0, N, C, H * W, float(eps), float(momentum), int(relu))
+        backend.run("bbd_bn_act_grouped%s_fwd" % groups.infix, x, ptr(x), ptr(residual), ptr(weight), ptr(bias), ptr(y),
+                    ptr(mean), ptr(invstd), ptr(running_mean), ptr(running_var), ptr(batches), ptr(scratch),
+                    *groups.fwd_args(), N, C, H * W, float(eps), float(momentum), int(relu))
         # without a residual the backward re-derives the ReLU mask from x (one activation read less per launch)
         ctx.save_for_backward(x, y if (relu and residual is not None) else None, weight, bias, mean, invstd)
-        ctx.meta = (bool(relu), residual is not None, backend, rows)
+        ctx.meta = (bool(relu), residual is not None, backend, groups)
         return y
 
     @staticmethod
     def backward(ctx, grad_y):
         x, y, weight, bias, mean, invstd = ctx.saved_tensors
-        relu, has_res, backend, rows = ctx.meta
+        relu, has_res, backend, groups = ctx.meta
         N, C, H, W = x.shape
         grad_y = grad_y.contiguous()
         grad_x = torch.empty_like(x)
         grad_res = torch.empty_like(x) if has_res else None
         grad_w = torch.empty(C, device=x.device, dtype=torch.float32)
         grad_b = torch.empty(C, device=x.device, dtype=torch.float32)
-        if isinstance(rows, tuple):                     # device group table (bn_call_groups_device)
-            table, G, biggest = rows
-            scratch = torch.empty(backend.lib.bn_grouped_scratch_doubles(biggest, G, C, H * W), device=x.device,
-                                  dtype=torch.float64)
-            backend.run("bbd_bn_act_grouped_dev_bwd", x, ptr(x), ptr(y), ptr(grad_y), ptr(weight), ptr(bias), ptr(mean),
-                        ptr(invstd), ptr(grad_x), ptr(grad_res), ptr(grad_w), ptr(grad_b), ptr(scratch), ptr(table), G,
-                        biggest, N, C, H * W, int(relu))
-            return grad_x, grad_w, grad_b, grad_res, None, None, None, None, None, None, None
-        G = len(rows)
-        scratch = torch.empty(backend.lib.bn_grouped_scratch_doubles(max(rows), G, C, H * W), device=x.device,
+        scratch = torch.empty(backend.lib.bn_grouped_scratch_doubles(groups.biggest, groups.G, C, H * W), device=x.device,
                               dtype=torch.float64)
-        backend.run("bbd_bn_act_grouped_bwd", x, ptr(x), ptr(y), ptr(grad_y), ptr(weight), ptr(bias), ptr(mean),
-                    ptr(invstd), ptr(grad_x), ptr(grad_res), ptr(grad_w), ptr(grad_b), ptr(scratch), _group_table(rows),
-                    G, N, C, H * W, int(relu))
+        backend.run("bbd_bn_act_grouped%s_bwd" % groups.infix, x, ptr(x), ptr(y), ptr(grad_y), ptr(weight), ptr(bias),
+                    ptr(mean), ptr(invstd), ptr(grad_x), ptr(grad_res), ptr(grad_w), ptr(grad_b), ptr(scratch),
+                    *groups.bwd_args(), N, C, H * W, int(relu))
         return grad_x, grad_w, grad_b, grad_res, None, None, None, None, None, None, None
 
 
@@ -1401,13 +1401,6 @@ def stem_supported(x, rows):
             and rows * x.shape[2] * x.shape[3] > _lib.STEM_MIN_ELEMS)
 
 
-def _stem_rows(N):
-    """largest call group of the batched pass being run"""
-    if _bn_device is not None:
-        return _bn_device[2]
-    return max(_bn_groups) if _bn_groups is not None else N
-
-
 class _StemBnReluPool(torch.autograd.Function):
     """`maxpool3s2(batch_norm_act(x, ..., relu=True))` with the pool inside the BatchNorm launches (csrc/bbd_nn.hip,
     bbd_stem_*): two launches each way, y written only on request, no full-size gradient of the pool."""
@@ -1421,55 +1414,34 @@ class _StemBnReluPool(torch.autograd.Function):
         y = torch.empty_like(x) if want_y else None
         pooled = torch.empty(N, C, OH, OW, device=x.device, dtype=torch.float32)
         code = torch.empty(N, C, OH, OW, device=x.device, dtype=torch.uint8)
-        if _bn_device is not None:
-            table, G, biggest = _bn_device
-            assert _bn_groups is None and biggest <= N
-            rows = (table, G, biggest)
-        else:
-            rows = _bn_groups if _bn_groups is not None else [N]
-            assert sum(rows) == N, "ops.bn_call_groups does not describe this batch (%s vs %d rows)" % (rows, N)
-            G, biggest = len(rows), max(rows)
-        mean = torch.empty(G, C, device=x.device, dtype=torch.float32)
-        invstd = torch.empty(G, C, device=x.device, dtype=torch.float32)
-        scratch = torch.empty(backend.lib.bn_grouped_scratch_doubles(biggest, G, C, H * W), device=x.device,
+        groups = call_groups(N).check(N)
+        mean = torch.empty(groups.G, C, device=x.device, dtype=torch.float32)
+        invstd = torch.empty(groups.G, C, device=x.device, dtype=torch.float32)
+        scratch = torch.empty(backend.lib.bn_grouped_scratch_doubles(groups.biggest, groups.G, C, H * W), device=x.device,
                               dtype=torch.float64)
-        if isinstance(rows, tuple):
-            backend.run("bbd_stem_dev_fwd", x, ptr(x), ptr(weight), ptr(bias), ptr(y), ptr(pooled), ptr(code), ptr(mean),
-                        ptr(invstd), ptr(running_mean), ptr(running_var), ptr(batches), ptr(scratch), ptr(rows[0]), G,
-                        biggest, N, C, H, W, float(eps), float(momentum))
-        else:
-            backend.run("bbd_stem_fwd", x, ptr(x), ptr(weight), ptr(bias), ptr(y), ptr(pooled), ptr(code), ptr(mean),
-                        ptr(invstd), ptr(running_mean), ptr(running_var), ptr(batches), ptr(scratch), _group_table(rows), G,
-                        _bn_untracked if _bn_groups is not None else 0, N, C, H, W, float(eps), float(momentum))
+        backend.run("bbd_stem%s_fwd" % groups.infix, x, ptr(x), ptr(weight), ptr(bias), ptr(y), ptr(pooled), ptr(code),
+                    ptr(mean), ptr(invstd), ptr(running_mean), ptr(running_var), ptr(batches), ptr(scratch),
+                    *groups.fwd_args(), N, C, H, W, float(eps), float(momentum))
         ctx.save_for_backward(x, code, weight, bias, mean, invstd)
-        ctx.meta = (backend, rows)
+        ctx.meta = (backend, groups)
         ctx.set_materialize_grads(False)
         return y, pooled
 
     @staticmethod
     def backward(ctx, grad_y, grad_pooled):
         x, code, weight, bias, mean, invstd = ctx.saved_tensors
-        backend, rows = ctx.meta
+        backend, groups = ctx.meta
         N, C, H, W = x.shape
         grad_y = grad_y.contiguous() if grad_y is not None else None
         grad_pooled = grad_pooled.contiguous() if grad_pooled is not None else None
         grad_x = torch.empty_like(x)
         grad_w = torch.empty(C, device=x.device, dtype=torch.float32)
         grad_b = torch.empty(C, device=x.device, dtype=torch.float32)
-        if isinstance(rows, tuple):
-            table, G, biggest = rows
-            scratch = torch.empty(backend.lib.bn_grouped_scratch_doubles(biggest, G, C, H * W), device=x.device,
-                                  dtype=torch.float64)
-            backend.run("bbd_stem_dev_bwd", x, ptr(x), ptr(grad_y), ptr(grad_pooled), ptr(code), ptr(weight), ptr(bias),
-                        ptr(mean), ptr(invstd), ptr(grad_x), ptr(grad_w), ptr(grad_b), ptr(scratch), ptr(table), G, biggest,
-                        N, C, H, W)
-        else:
-            G = len(rows)
-            scratch = torch.empty(backend.lib.bn_grouped_scratch_doubles(max(rows), G, C, H * W), device=x.device,
-                                  dtype=torch.float64)
-            backend.run("bbd_stem_bwd", x, ptr(x), ptr(grad_y), ptr(grad_pooled), ptr(code), ptr(weight), ptr(bias),
-                        ptr(mean), ptr(invstd), ptr(grad_x), ptr(grad_w), ptr(grad_b), ptr(scratch), _group_table(rows), G,
-                        N, C, H, W)
+        scratch = torch.empty(backend.lib.bn_grouped_scratch_doubles(groups.biggest, groups.G, C, H * W), device=x.device,
+                              dtype=torch.float64)
+        backend.run("bbd_stem%s_bwd" % groups.infix, x, ptr(x), ptr(grad_y), ptr(grad_pooled), ptr(code), ptr(weight),
+                    ptr(bias), ptr(mean), ptr(invstd), ptr(grad_x), ptr(grad_w), ptr(grad_b), ptr(scratch),
+                    *groups.bwd_args(), N, C, H, W)
         return grad_x, grad_w, grad_b, None, None, None, None, None, None, None
 
 

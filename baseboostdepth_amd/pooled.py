@@ -90,7 +90,8 @@ class PooledTables:
     def __init__(self, plan, frames, frame_ids, incremental, partial, decomp, maxing, caps, layout, pad_quantum, early_rows,
                  pinned):
         B = plan.B
-        assert B == caps.B
+        if B != caps.B:
+            raise ValueError("a batch of %d samples, tables for %d" % (B, caps.B))
         sched = steptables.PoseSchedule(plan, frame_ids, incremental, partial, decomp, chunk=1 << 30)
         self.plan, self.schedule = plan, sched
         if len(sched.requests) > MAX_REQUESTS:
@@ -142,13 +143,14 @@ class PooledTables:
         while pad > 0:
             rows.append(min(pad, self.bound))
             pad -= rows[-1]
-        assert len(rows) <= ops.BN_MAX_GROUPS and (not sched.rows or max(sched.rows) <= self.bound)
         self.G = SMALL_GROUPS if len(rows) <= SMALL_GROUPS else ops.BN_MAX_GROUPS
-        assert not early or self.G == SMALL_GROUPS
+        if len(rows) > ops.BN_MAX_GROUPS or (early and self.G != SMALL_GROUPS):
+            raise ValueError("more call groups than the group grid holds")
         g = sec("groups")
         g[1:len(rows) + 1] = np.cumsum(rows)
         g[len(rows) + 1:ops.BN_MAX_GROUPS + 1] = R
         g[ops.BN_MAX_GROUPS + 1] = len(sched.rows)          # tracked groups = the real calls
+        ops.check_group_table(g, self.G, self.bound, R)     # (a pose-network call above `bound` rows, among others)
 
         # ---- composition table (chains / T_error / partial swap), padded with constant no-op rows
         self.pose_views = []                   # (output key, "M" | "out", first row, rows, constant)
@@ -191,7 +193,8 @@ class PooledTables:
                     continue
                 buf, o0, n = where[("cam_T_cam" if kind == "T" else "cam_T_cam_error", 0, f)]
                 r = plan.job_rows_in_source(f)[j] if per_source_rows else j
-                assert r < n
+                if r >= n:
+                    raise ValueError("a pose-table row past its source's rows")
                 tsel[p0 + j] = src_off[buf] + o0 + r
         if plan.NP > caps.NP or plan.NI > caps.NI:
             raise ValueError("more pose rows / identity maps than the tables hold")
