@@ -45,6 +45,7 @@ SRCS = _here("""
     bbd_wgrad.hip
     bbd_up2conv.hip
     bbd_sgm.hip
+    bbd_align.hip
 """)
 OUT = os.path.join(HERE, "libbbd_hip.so")
 # every header of this directory: one that is forgotten here would leave a stale library behind an edit

@@ -24,8 +24,8 @@ import torch
 
 from . import ops
 from .tables import split64, upload
-from ._lib import (EVAL_DESC, EVAL_OUT, EVAL_PRED_IS_DISP, EVAL_MEDIAN_MIDPOINT, EVAL_NO_MEDIAN_SCALING, SYNS_OUT,
-                   SYNS_CLOUD_OUT, SYNS_RAYS_PIXEL, TRAJ_MAX_LEN, TRAJ_MODES, BbdError, ptr)
+from ._lib import (ALIGN_OUT, EVAL_DESC, EVAL_OUT, EVAL_PRED_IS_DISP, EVAL_MEDIAN_MIDPOINT, EVAL_NO_MEDIAN_SCALING,
+                   SYNS_OUT, SYNS_CLOUD_OUT, SYNS_RAYS_PIXEL, TRAJ_MAX_LEN, TRAJ_MODES, BbdError, ptr)
 
 METRIC_NAMES = ["de/abs_rel", "de/sq_rel", "de/rms", "de/log_rms", "da/a1", "da/a2", "da/a3"]   # trainer.py:156
 GARG_CROP = (0.40810811, 0.99189189, 0.03594771, 0.96405229)     # trainer.py:603-604
@@ -111,6 +111,34 @@ def depth_metrics(pred, gts, indices, min_depth=1e-3, max_depth=80.0, clamp=(1e-
             (0 if median_scaling else EVAL_NO_MEDIAN_SCALING)
     backend.run("bbd_depth_metrics", pred, ptr(pred), ptr(gts.buffer), ptr(desc), ptr(out), n, h, w,
                 float(min_depth), float(max_depth), float(clamp[0]), float(clamp[1]), float(scale_factor), flags)
+    return out
+
+
+# the columns of a `depth_metrics_affine` row (BBD_ALIGN_OUT): the count stands where a `depth_metrics` row has it
+ALIGN_COLUMNS = ["abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3", "scale", "shift", "silog", "count", "irmse"]
+
+
+def depth_metrics_affine(pred_disp, gts, indices, min_depth=1e-3, max_depth=80.0, backend=None):
+    """Scores pred_disp[i] ([n,1,h,w] or [n,h,w]), a disparity-like map in ANY affine gauge (a relative-depth model's
+    output), against gts[indices[i]]: per image the scale and shift that fit it to 1 / ground truth by least squares on
+    the pixels `depth_metrics` scores, then the errors of the aligned depth.  One
+    `bbd_depth_metrics_affine` launch; returns a float64 [n, 12] device tensor with the columns `ALIGN_COLUMNS`
+    (silog in percent, irmse in 1/km).  An image with fewer than two scored pixels or a constant prediction has NaNs
+    and its count."""
+    backend = backend or ops.default_backend()
+    pred = pred_disp.detach()
+    if pred.dim() == 4:
+        assert pred.shape[1] == 1
+        pred = pred[:, 0]
+    pred = pred.contiguous().float()
+    backend._check(pred, gts.buffer)
+    n, h, w = pred.shape
+    idx = torch.as_tensor(indices, dtype=torch.long, device=gts.desc.device).view(-1)
+    assert idx.numel() == n
+    desc = gts.desc.index_select(0, idx).contiguous()
+    out = torch.empty(n, ALIGN_OUT, device=pred.device, dtype=torch.float64)
+    backend.run("bbd_depth_metrics_affine", pred, ptr(pred), ptr(gts.buffer), ptr(desc), ptr(out), n, h, w,
+                float(min_depth), float(max_depth), 0)
     return out
 
 
@@ -315,12 +343,26 @@ def evaluate(opt, dataloader=None, gt_depths=None, models=None, batch_size=16, g
     intrinsics at the ground-truth size, SYNS the dataset's; `cloud_rays` ("pixel" | "reference") chooses the pairing of
     pixels and rays (`pointcloud_metrics`).  It needs the metrics rows, so it is refused together with `no_eval`.
 
-    `scale_recovery` ("median" | "ground"): under "ground" a KITTI mono prediction is scaled without
+    `scale_recovery` ("median" | "ground" | "lsq"): under "ground" a KITTI mono prediction is scaled without
     ground truth - every batch goes through `ops.ground_scale` with the KITTI intrinsics of the prediction's own size
     (`camera_height` 1.65, `ground_angle` 5.0), its disparities are divided on the device by the scale of their image
     and scored without median scaling; `save_clouds` exports those scaled disparities.  The ratios line and the
     returned ratios are the recovered scales; an image without ground has a NaN scale, is named in a warning and left
     out of the mean.  Refused with `eval_stereo`, `disable_median_scaling` and the SYNS split.
+
+    `scale_recovery` "lsq"  is the protocol of the relative-depth models (MiDaS, DPT, Depth Anything),
+    whose disparity is known up to a scale AND a shift: every batch is scored by one `bbd_depth_metrics_affine` launch
+    (`depth_metrics_affine`) in place of `bbd_depth_metrics` - per image the least-squares scale and shift that map the
+    prediction to the inverse ground truth on the scored pixels, the aligned disparity capped at 1 / 80, then the seven
+    errors, SILog and iRMSE - and the rows are read back once.  Printed: a warning that names the images that could not
+    be aligned (fewer than two scored pixels, a constant or a non-finite prediction; left out of the means), a warning
+    that names the images with scale <= 0 (scored, in the means), ` Alignment | scale med | shift med` in place of the
+    ratios line, the seven-metric table, and a line with silog (percent) and irmse (1/km).  Returns (mean_errors[7],
+    alignment [N, 2] = scale and shift, NaN rows for the images without alignment).  `post_process`,
+    `save_pred_disps` (the unaligned disparities), `ext_disp_to_eval` and `no_eval` behave as under "median".  Refused
+    (`options.alignment_conflict`) with `eval_stereo`, `disable_median_scaling`, a `pred_depth_scale_factor` other
+    than 1, the SYNS split, `save_clouds` and the uncertainty options: their kernels read the median ratio of a
+    metrics row and know no shift.
 
     Uncertainty (KITTI splits only), each field read with a default:
       `uncertainty`        "none" | "post": under "post" every batch runs with its flipped copy (`post_process` is
@@ -336,7 +378,8 @@ def evaluate(opt, dataloader=None, gt_depths=None, models=None, batch_size=16, g
     writes.  Refused with the SYNS split, `no_eval` and `scale_recovery ground`.
 
     `backend` and `device` are for tests (the host ports); by default the HIP backend and `cuda:<opt.cuda>`."""
-    uncert = _uncert_options(opt)                                        # raises before anything is touched
+    _align_options(opt)                                                  # raises before anything is touched
+    uncert = _uncert_options(opt)                                        # as well
     from . import tuning
     tuning.use_shipped_db()      # (no Trainer is built here: the tuned MIOpen database is wired explicitly)
     import os
@@ -547,10 +590,10 @@ class _CloudSaver:
 
 
 def _ground_options(opt):
-    """`scale_recovery == "ground"` -> the keywords of `ops.ground_scale`; "median" (or an `opt` without the field) ->
-    None.  What the scale would collide with is refused."""
+    """`scale_recovery == "ground"` -> the keywords of `ops.ground_scale`; "median" (or an `opt` without the field) and
+    "lsq" (which has options of its own: `_align_options`) -> None.  What the scale would collide with is refused."""
     mode = getattr(opt, "scale_recovery", "median")
-    if mode == "median":
+    if mode in ("median", "lsq"):                         # lsq: `_align_options`
         return None
     if mode != "ground":
         raise ValueError("scale_recovery is median or ground, got %r" % (mode,))
@@ -578,6 +621,44 @@ def _ground_summary(rows, ground_rows):
     print("\n  " + ("{:>8} | " * 7).format("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3"))
     print(("&{: 8.3f}  " * 7).format(*mean_errors.tolist()) + "\\\\")
     return mean_errors, ratios
+
+
+def _align_options(opt):
+    """Is the split scored under `scale_recovery lsq`?  What that collides with is refused
+    (`options.alignment_conflict`)."""
+    from .options import alignment_conflict
+    conflict = alignment_conflict(opt)
+    if conflict:
+        raise ValueError(conflict)
+    return getattr(opt, "scale_recovery", "median") == "lsq"
+
+
+def _align_summary(rows):
+    """The printed summary and the result of a split scored under `scale_recovery lsq` from its float64 rows
+    [N, 12] (`ALIGN_COLUMNS`): the mean over the images that could be aligned - the others are counted and named - and
+    the alignment line in place of the ratios line.  Returns (mean_errors[7], alignment [N, 2] = scale, shift)."""
+    alignment = rows[:, 7:9].copy()
+    fitted = ~np.isnan(rows[:, :10]).any(1) & ~np.isnan(rows[:, 11])
+    if not fitted.all():
+        lost = np.nonzero(~fitted)[0]
+        print("   WARNING: no alignment for {:d} of {:d} images (fewer than two scored pixels, a constant or a non-finite "
+              "prediction), left out of the means: {}".format(len(lost), len(rows), ", ".join(str(i) for i in lost)))
+    with np.errstate(invalid="ignore"):
+        flipped = np.nonzero(fitted & (rows[:, 7] <= 0))[0]
+    if len(flipped):
+        print("   WARNING: scale <= 0 in {:d} of {:d} images - the prediction is anti-correlated with the inverse ground "
+              "truth; they are scored and stay in the means: {}".format(len(flipped), len(rows),
+                                                                        ", ".join(str(i) for i in flipped)))
+    if fitted.any():
+        print(" Alignment | scale med: {:0.4g} | shift med: {:0.4g}".format(np.median(rows[fitted, 7]),
+                                                                          np.median(rows[fitted, 8])))
+    mean = rows[fitted].mean(0) if fitted.any() else np.full(rows.shape[1], np.nan)
+    mean_errors = mean[:7]
+    print("\n  " + ("{:>8} | " * 7).format("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3"))
+    print(("&{: 8.3f}  " * 7).format(*mean_errors.tolist()) + "\\\\")
+    print("  " + ("{:>8} | " * 2).format("silog", "irmse"))
+    print(("&{: 8.3f}  " * 2).format(mean[9], mean[11]) + "\\\\")
+    return mean_errors, alignment
 
 
 UNCERT_METRICS = ("abs_rel", "rmse", "a1")
@@ -662,6 +743,20 @@ def _evaluate_kitti(opt, source, save_path, no_eval, gt_depths, split_dir, devic
         median_scaling, scale = False, 1
     rows, ground_rows, kept, first = [], [], [], 0
     spars, kept_uncerts = [], []
+    if _align_options(opt):                               # the fit is the scaling: one launch per batch, its own rows
+        with torch.no_grad():
+            for pred_disp in source:
+                n = pred_disp.shape[0]
+                if save_path is not None:
+                    kept.append(pred_disp)                # the unaligned disparities
+                rows.append(depth_metrics_affine(pred_disp, gts, list(range(first, first + n)), min_depth=1e-3,
+                                                 max_depth=80.0, backend=backend))
+                first += n
+        if save_path is not None:
+            _save_disps(kept, save_path)
+        rows = torch.cat(rows).cpu().numpy()              # the only host synchronisation of the scoring
+        assert first == len(gts), "split has %d images, ground truth %d" % (first, len(gts))
+        return _align_summary(rows)
     with torch.no_grad():
         for pred_disp in source:
             if uncert is not None:

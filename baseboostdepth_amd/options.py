@@ -77,8 +77,10 @@ _FLAGS = [
     ("--cloud_stride", dict(type=int, default=1)),
     ("--cloud_rays", dict(type=str, default="pixel", choices=["pixel", "reference"])),
     # evaluate_depth.py: where the scale of a mono prediction comes from - the LiDAR median of every image (the
-    # reference), or the camera's height above the pixels found to be road, without ground truth
-    ("--scale_recovery", dict(type=str, default="median", choices=["median", "ground"])),
+    # reference), or the camera's height above the pixels found to be road, without ground truth, or - for
+    # the relative-depth models, whose disparity is known up to a scale AND a shift - the least-squares fit of every
+    # image to its inverse ground truth (lsq), which also prints SILog and iRMSE
+    ("--scale_recovery", dict(type=str, default="median", choices=["median", "ground", "lsq"])),
     ("--camera_height", dict(type=float, default=1.65)), ("--ground_angle", dict(type=float, default=5.0)),
     # evaluate_depth.py: a ground-truth-free uncertainty map of every prediction, judged by sparsification (AUSE / AURG,
     # DESIGN.md 6n).  post = |d - flip(d')| of the flip pass (implies --post_process); --ext_uncert_to_eval supplies the
@@ -127,6 +129,29 @@ def uncertainty_conflict(opt):
     K = get("sparsification_intervals", 50)
     if not isinstance(K, int) or not 1 <= K <= SPARSIFICATION_MAX_INTERVALS:
         return "sparsification_intervals must be 1 ... %d, got %r" % (SPARSIFICATION_MAX_INTERVALS, K)
+    return None
+
+
+def alignment_conflict(opt):
+    """What `scale_recovery lsq` collides with in `opt`, as one sentence, or None.  Every field is read with its default,
+    so an `opt` without them has no conflict.  `options.parse` and `evaluation.evaluate` both refuse with it."""
+    get = lambda name, default: getattr(opt, name, default)      # noqa: E731
+    if get("scale_recovery", "median") != "lsq":
+        return None
+    for name in ("eval_stereo", "disable_median_scaling"):
+        if get(name, False):
+            return ("--scale_recovery lsq fits the scale and the shift of every image to its ground truth: the alignment "
+                    "is the scaling, so it excludes --%s" % name)
+    if get("pred_depth_scale_factor", 1) != 1:
+        return ("--scale_recovery lsq fits the scale of every image itself: a --pred_depth_scale_factor other than 1 "
+                "would be fitted away")
+    for name, set_ in (("--eval_split SYNS", get("eval_split", "eigen") == "SYNS"),
+                       ("--save_clouds", get("save_clouds", None) is not None),
+                       ("--uncertainty", get("uncertainty", "none") != "none"),
+                       ("--ext_uncert_to_eval", get("ext_uncert_to_eval", None) is not None)):
+        if set_:
+            return ("--scale_recovery lsq excludes %s: its kernels read the median ratio of a bbd_depth_metrics row and "
+                    "know no shift" % name)
     return None
 
 
@@ -239,6 +264,9 @@ class MonodepthOptions:
                                       "height above the road: it excludes %s" % flag)
             if not self.options.camera_height > 0 or not 0.0 <= self.options.ground_angle < 90.0:
                 self.parser.error("--camera_height must be positive and --ground_angle lie in [0, 90) degrees")
+        conflict = alignment_conflict(self.options)
+        if conflict:
+            self.parser.error(conflict)
         conflict = uncertainty_conflict(self.options)
         if conflict:
             self.parser.error(conflict)

@@ -60,8 +60,9 @@ extern "C" {
  * 24 = bbd_conv3x3_wgrad (the decoder's 3x3 weight gradients from the NCHW tensors);
  * 25 = bbd_geo_fwd / bbd_geo_bwd (the geometry-consistency loss for training, forward and backward);
  * 26 = bbd_up2conv3x3_fwd / _bwd (the decoder's finest up-sample + pad + 3x3 convolution in sub-pixel form);
- * 27 = bbd_sgm_hints (semi-global stereo matching: proxy disparities for --depth_hints). */
-#define BBD_ABI_VERSION 27
+ * 27 = bbd_sgm_hints (semi-global stereo matching: proxy disparities for --depth_hints);
+ * 28 = bbd_depth_metrics_affine (depth evaluation under a per-image least-squares scale and shift). */
+#define BBD_ABI_VERSION 28
 
 /* Source frames live in separate tensors, one per frame id (inputs[("color", f, 0)],
  * trainer.py:428).  A "slot" indexes a host array of their base pointers. */
@@ -881,6 +882,34 @@ int bbd_post_process_uncert(const float* disp, float* out, float* uncert, int n,
 int bbd_sparsification(const float* pred, const float* uncert, const float* gt, const int32_t* desc, const float* rows,
                        double* out, void* scratch, long scratch_bytes, int n, int h, int w, int intervals,
                        double min_depth, double max_depth, double scale_factor, int flags, void* stream);
+
+/* ---- Affine-invariant depth evaluation (csrc/bbd_align.hip, evaluation.depth_metrics_affine): the protocol
+ * of the relative-depth models (MiDaS, DPT, Depth Anything), whose prediction is a disparity up to an unknown scale AND
+ * shift.  Arithmetic and the order of every addition: csrc/bbd_align_math.h.
+ *
+ * pred is float32 [n,h,w], a disparity-like map in any affine gauge; gt and desc are the ragged ground truth and the
+ * BBD_EVAL_DESC table of bbd_depth_metrics.  The pixels of image i are the N pixels bbd_depth_metrics scores (inside the
+ * crop window cut to the map, min_depth < g < max_depth in float32).  Per pixel
+ *   x = the cv2-style linear resize of pred[i] at (y, x), float32: no reciprocal, no scale factor;  t = 1.0 / (double)g
+ * and, in float64, the centred two-sweep least squares of t on x:
+ *   mx = sum x / N, mt = sum t / N;  scale = sum (x - mx)(t - mt) / sum (x - mx)^2;  shift = mt - scale * mx
+ *   a = scale * x + shift;  a = a < 1 / max_depth ? 1 / max_depth : a      the disparity cap: a pixel the fit sends to
+ *                                                                          zero or below is scored at max_depth
+ *   p = (float)(1.0 / a), clamped to [min_depth, max_depth] in float32
+ * then the seven summands of bbd_depth_metrics (float32 operations, float64 sums) and, with d = logf(p) - logf(g),
+ *   silog = 100 sqrt(max(sum d^2 / N - (sum d / N)^2, 0))      irmse = 1000 sqrt(sum (1/p - 1/g)^2 / N)   (1/km for metres)
+ * out is float64 [n, BBD_ALIGN_OUT]:
+ *   {abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, scale, shift, silog, count N, irmse}
+ * An image with N < 2 or max x == min x is degenerate: quiet NaNs, the count kept (0 where nothing is scored).  A
+ * non-finite x among the scored pixels is not caught: it makes the fit, and with it every column but the count, NaN.
+ * One 1024-thread workgroup per image, three sweeps, no scratch, no atomics, no host synchronisation; every float64 sum
+ * is taken in an order that depends on the window alone - identical calls give identical bytes.
+ *
+ * flags must be 0.  Returns BBD_E_BADARG and launches nothing for a NULL pointer, n <= 0, h or w below 1, a flag, or
+ * unless 0 <= min_depth < max_depth. */
+#define BBD_ALIGN_OUT 12
+int bbd_depth_metrics_affine(const float* pred, const float* gt, const int32_t* desc, double* out, int n, int h, int w,
+                             double min_depth, double max_depth, int flags, void* stream);
 
 /* ---- KITTI odometry evaluation (evaluate_pose.py:18-41, :101-116, :125-159): everything after the pose
  * network, for all windows of a sequence in one call - three small launches, no host synchronisation, no atomics
