@@ -74,8 +74,7 @@ class ReflectionPad1(nn.ReflectionPad2d):
         super().__init__(1)
 
     def forward(self, x):
-        if (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and min(x.shape[2:]) >= 2 and ops.FUSED_NN
-                and x.shape[0] * x.shape[1] <= 65535):
+        if ops.reflect_pad1_supported(x):
             return ops.reflect_pad1(x)
         return super().forward(x)
 
@@ -89,13 +88,20 @@ class Conv3x3(nn.Module):
         self.conv = nn.Conv2d(int(in_channels), int(out_channels), 3)
 
     def _fused(self, x):
-        return (self.conv.out_channels == 1 and x.is_cuda and x.dtype == torch.float32 and ops.FUSED_NN
-                and isinstance(self.pad, ReflectionPad1) and self.conv.in_channels <= 256 and min(x.shape[2:]) >= 2)
+        """Is this a disparity head (one output channel behind a reflection border) on a tensor the HIP head takes?"""
+        return (self.conv.out_channels == 1 and isinstance(self.pad, ReflectionPad1)
+                and ops.disp_head_supported(x, self.conv.in_channels))
 
     def forward(self, x):
         if self._fused(x):
             return ops.dispconv(x, self.conv.weight, self.conv.bias)    # disparity head: one streaming kernel
         return self.conv(self.pad(x))
+
+    def disparity(self, x):
+        """sigmoid(self(x)); a disparity head does the convolution and its sigmoid in ONE HIP pass each way."""
+        if self._fused(x):
+            return ops.disp_head(x, self.conv.weight, self.conv.bias)
+        return torch.sigmoid(self(x))
 
 
 class ConvBlock(nn.Module):
@@ -107,9 +113,11 @@ class ConvBlock(nn.Module):
         self.conv = Conv3x3(in_channels, out_channels)
         self.nonlin = nn.ELU(inplace=True)
 
-    def _fused(self, x):
-        return (x.is_cuda and x.dtype == torch.float32 and ops.FUSED_NN and self.conv.conv.out_channels > 1
-                and self.conv.conv.bias is not None and (x.shape[2] * x.shape[3]) % 4 == 0)
+    def _fused(self, x, border=0):
+        """Do bias + ELU run as `ops.bias_elu_` on the convolution of `x` (which carries `border` pixels of padding)?  A
+        one-channel block leaves an `x` without its border to `Conv3x3`'s disparity head."""
+        conv = self.conv.conv
+        return conv.bias is not None and (border > 0 or conv.out_channels > 1) and ops.bias_elu_supported(x, border)
 
     def forward(self, x):
         if self._fused(x):
@@ -118,11 +126,17 @@ class ConvBlock(nn.Module):
 
     def forward_padded(self, xp):
         """`xp` already carries the 1-pixel reflection border (e.g. from `ops.upcat_pad`)."""
-        conv = self.conv.conv
-        out_hw = (xp.shape[2] - 2) * (xp.shape[3] - 2)
-        if xp.is_cuda and xp.dtype == torch.float32 and ops.FUSED_NN and conv.bias is not None and out_hw % 4 == 0:
+        if self._fused(xp, 1):
             return self.bias_act_(self.conv_raw(xp))
-        return self.nonlin(conv(xp))
+        return self.nonlin(self.conv.conv(xp))
+
+    def forward_upcat(self, x, skip=None):
+        """self(cat(nearest_x2(x), skip)); up-sampling, concatenation and this block's reflection border are ONE HIP pass
+        where `ops.upcat_pad` takes the tensors."""
+        if ops.upcat_pad_supported(x, skip):
+            return self.forward_padded(ops.upcat_pad(x, skip))
+        x = upsample(x)
+        return self(x if skip is None else torch.cat([x, skip], 1))
 
     def conv_raw(self, xp):
         """The bias-free convolution of the padded input: what `bias_act_` and the decoder's fused glue start from.

@@ -42,54 +42,47 @@ class DepthDecoder(nn.Module):
     def _stage(self, *key):
         return self.decoder[self._slot[key]]
 
-    def _glue_level(self, level, x):
-        """Do both ConvBlocks of `level` start from a bias-free convolution of input `x`, so that bias + ELU can move
-        into the glue passes (BBD_FUSED_DECODER_GLUE=0: never)?"""
-        return (ops.FUSED_DECODER_GLUE and self._stage("upconv", level, 0)._fused(x)
-                and self._stage("upconv", level, 1).conv.conv.bias is not None)
+    def _glued(self, level, x):
+        """Can bias + ELU of both ConvBlocks of `level` move into the glue passes around them?  Both must start from a
+        bias-free convolution (of `x`, resp. of the concatenation) and have a bias.  ops.FUSED_DECODER_GLUE selects
+        between two fused forms: off (BBD_FUSED_DECODER_GLUE=0), every level takes `_plain`, as before the glue kernels."""
+        first, second = self._stage("upconv", level, 0), self._stage("upconv", level, 1)
+        return ops.FUSED_DECODER_GLUE and first._fused(x) and second.conv.conv.bias is not None
+
+    def _plain(self, level, x, skip):
+        """Each block with its own bias + ELU pass: first(x), then up-sample + concatenate + second."""
+        return self._stage("upconv", level, 1).forward_upcat(self._stage("upconv", level, 0)(x), skip)
+
+    def _level(self, level, x, xp, skip):
+        """One decoder level: (x, xp) of the level above -> (x, xp) of this one.  `xp` is `x` with its reflection border
+        where the level above wrote both in one pass (`ops.bias_elu_pad`), None wherever it did not: after a level that
+        is not glued, in front of a level that is not, and below level 0."""
+        if not self._glued(level, x):
+            return self._plain(level, x, skip), None
+        first, second = self._stage("upconv", level, 0), self._stage("upconv", level, 1)
+        bias = first.conv.conv.bias
+        z = first.conv_raw(xp if xp is not None else first.conv.pad(x))
+        if not ops.upcat_pad_act_supported(z, bias, skip):
+            # glue refused for this level (too many planes for one launch): what `_plain` does from `z` on
+            return second.forward_upcat(first.bias_act_(z), skip), None
+        # glued: conv -> upcat_pad_act -> conv -> bias_elu_pad, the blocks' bias + ELU ride on the glue passes
+        if skip is None and ops.up2_conv3x3_routed(z, bias, second.conv.conv.weight):
+            # up-sample + border + convolution as four 2x2 convolutions of z: no up-sampled copy
+            z = ops.up2_conv3x3(z, bias, second.conv.conv.weight)
+        else:
+            z = second.conv_raw(ops.upcat_pad_act(z, bias, skip))
+        if level > 0 and self._glued(level - 1, z) and ops.bias_elu_pad_supported(z, second.conv.conv.bias):
+            return ops.bias_elu_pad(z, second.conv.conv.bias)
+        return second.bias_act_(z), None            # level 0: nothing pads its output
 
     def forward(self, input_features):
         self.outputs = {}
-        x = input_features[-1]
-        xp = None       # x with its reflection border, where the level above wrote both in one pass (ops.bias_elu_pad)
+        x, xp = input_features[-1], None
         for level in reversed(range(5)):
-            first, second = self._stage("upconv", level, 0), self._stage("upconv", level, 1)
             skip = input_features[level - 1] if (self.use_skips and level > 0) else None
-            glued = False
-            if self._glue_level(level, x):
-                # the blocks' bias + ELU ride on the glue passes: conv -> upcat_pad_act -> conv -> bias_elu_pad
-                z = first.conv_raw(xp if xp is not None else first.conv.pad(x))
-                glued = ops.upcat_pad_act_supported(z, first.conv.conv.bias, skip)
-                if not glued:
-                    x = first.bias_act_(z)              # what first(x) does
-            else:
-                x = first(x)
-            xp = None
-            if glued:
-                if skip is None and ops.up2_conv3x3_routed(z, first.conv.conv.bias, second.conv.conv.weight):
-                    # up-sample + border + convolution as four 2x2 convolutions of z: no up-sampled copy
-                    z = ops.up2_conv3x3(z, first.conv.conv.bias, second.conv.conv.weight)
-                else:
-                    z = second.conv_raw(ops.upcat_pad_act(z, first.conv.conv.bias, skip))
-                if level > 0 and self._glue_level(level - 1, z) and ops.bias_elu_pad_supported(z, second.conv.conv.bias):
-                    x, xp = ops.bias_elu_pad(z, second.conv.conv.bias)
-                else:
-                    x = second.bias_act_(z)             # level 0: nothing pads its output
-            elif ops.upcat_pad_supported(x, skip):
-                # nearest x2 + skip concatenation + the next block's reflection border in ONE HIP pass
-                x = self._stage("upconv", level, 1).forward_padded(ops.upcat_pad(x, skip))
-            else:
-                x = F.interpolate(x, scale_factor=2, mode="nearest")
-                if skip is not None:
-                    x = torch.cat([x, skip], 1)
-                x = self._stage("upconv", level, 1)(x)
+            x, xp = self._level(level, x, xp, skip)
             if level in self.scales:
-                head = self._stage("dispconv", level)
-                if head._fused(x):
-                    # convolution to one channel and its sigmoid in ONE HIP pass each way
-                    self.outputs[("disp", level)] = ops.disp_head(x, head.conv.weight, head.conv.bias)
-                else:
-                    self.outputs[("disp", level)] = torch.sigmoid(head(x))
+                self.outputs[("disp", level)] = self._stage("dispconv", level).disparity(x)
         return self.outputs
 
 

@@ -5,12 +5,11 @@ here with torchvision-identical module names - `conv1, bn1, layer{1..4}.{i}.conv
 layer{k}.0.downsample.{0,1}, fc` - so `encoder.pth` checkpoints written by the reference
 (trainer.py:783-805) load with `load_state_dict` unchanged, including the unused `fc`.
 """
-import os
-
 import numpy as np
-import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from .. import ops
 
 
 class FusedBatchNorm2d(nn.BatchNorm2d):
@@ -19,16 +18,18 @@ class FusedBatchNorm2d(nn.BatchNorm2d):
     launches each way (csrc/bbd_nn.hip) instead of MIOpen batch-norm + add + clamp kernels.  Host
     tensors, eval mode and exotic configurations take the stock PyTorch ops."""
 
-    fused = os.environ.get("BBD_FUSED_BN", "1") != "0"
+    fused = ops.switch("BBD_FUSED_BN")
+
+    def takes_fused_launches(self, x):
+        """Does this module, in its current mode, normalise `x` with the fused launches (`ops.batch_norm_act`, the stem)?"""
+        return (self.fused and self.training and self.affine and self.track_running_stats and self.momentum is not None
+                and ops.batch_norm_act_supported(x))
 
     def forward(self, x, residual=None, relu=False):
-        if (self.fused and x.is_cuda and self.training and self.affine and self.track_running_stats
-                and self.momentum is not None and x.dtype == torch.float32 and x.dim() == 4):
-            from .. import ops
+        if self.takes_fused_launches(x):
             return ops.batch_norm_act(x, self.weight, self.bias, residual, self.running_mean, self.running_var,
                                       self.momentum, self.eps, relu, num_batches_tracked=self.num_batches_tracked)
         if self.training and x.is_cuda:
-            from .. import ops
             if ops.call_groups(x.shape[0]).rows != (x.shape[0],):
                 raise RuntimeError("a batched pass with call groups needs the fused BatchNorm path")
         y = super().forward(x)
@@ -44,9 +45,7 @@ class MaxPool3s2(nn.MaxPool2d):
         super().__init__(kernel_size=3, stride=2, padding=1)
 
     def forward(self, x):
-        from .. import ops
-        if (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and ops.FUSED_NN
-                and x.shape[0] * x.shape[1] <= 65535):
+        if ops.maxpool3s2_supported(x):
             return ops.maxpool3s2(x)
         return super().forward(x)
 
@@ -154,12 +153,10 @@ class ResnetEncoder(nn.Module):
         (`ops.stem_bn_relu_pool`), else bn1 + ReLU and the max-pool as two."""
         e = self.encoder
         bn = e.bn1
-        if (isinstance(bn, FusedBatchNorm2d) and isinstance(e.maxpool, MaxPool3s2) and bn.fused and x.is_cuda and bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None
-                and x.dtype == torch.float32 and x.dim() == 4 and x.shape[0] * x.shape[1] <= 65535):
-            from .. import ops
-            if ops.FUSED_NN and ops.FUSED_STEM and ops.stem_supported(x, ops.call_groups(x.shape[0]).biggest):
-                return ops.stem_bn_relu_pool(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps,
-                                             want_y=self.stem_feature, num_batches_tracked=bn.num_batches_tracked)
+        if (isinstance(bn, FusedBatchNorm2d) and isinstance(e.maxpool, MaxPool3s2) and bn.takes_fused_launches(x)
+                and ops.stem_routed(x)):
+            return ops.stem_bn_relu_pool(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps,
+                                         want_y=self.stem_feature, num_batches_tracked=bn.num_batches_tracked)
         f0 = bn(x, relu=True)
         return (f0 if self.stem_feature else None), e.maxpool(f0)
 

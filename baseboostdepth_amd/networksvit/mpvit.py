@@ -195,7 +195,7 @@ class Patch_Embed_stage(nn.Module):
 
 def _hip_tokens(t):
     """fp32 GPU tokens take the HIP depth-wise kernels (BBD_FUSED_NN=0 keeps the MIOpen path for A/B runs)."""
-    return t.is_cuda and t.dtype == torch.float32 and ops.FUSED_NN
+    return ops.hip_fp32(t) and ops.FUSED_NN
 
 
 def _as_image(tokens, size):

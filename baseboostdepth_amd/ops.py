@@ -20,7 +20,24 @@ from .plan import frame_slot
 from .tables import join64, split64, upload
 
 
-# BBD_FUSED_NN=0 sends the encoder / decoder glue (pad, max-pool) back to the stock ATen kernels (A/B runs)
+def switch(name):
+    """A `BBD_FUSED_*` switch of the A/B runs: on unless the environment sets it to 0.  Every switch is a module global
+    (one class attribute: `FusedBatchNorm2d.fused`) initialised here, once, and read where a path is chosen; the list is
+    in INTEGRATION.md."""
+    return os.environ.get(name, "1") != "0"
+
+
+def hip_fp32(*tensors):
+    """Is every argument that is not None a float32 tensor on the GPU - the only kind the network ops below take?"""
+    return all(t is None or (t.is_cuda and t.dtype == torch.float32) for t in tensors)
+
+
+# The y extent of a launch grid.  The pad, pool and glue entry points put one plane (sample x channel) there, the stem one
+# channel, the disparity head one sample, and refuse more with BBD_E_BADARG (csrc/bbd_nn.hip, the `> 65535` tests of the
+# bbd_* functions at its end; include/bbd_hip.h where it documents the limit).  The `*_supported` predicates use this name.
+MAX_PLANES = 65535
+
+
 def _experiment(name, default):
     """Experiment knobs of the A/B tooling (tools/*.sh) are read only under BBD_EXPERIMENT=1: a stray variable in a
     user's environment cannot put the shipped library into a configuration no test covers."""
@@ -29,8 +46,8 @@ def _experiment(name, default):
     return os.environ.get(name, default)
 
 
-FUSED_NN = os.environ.get("BBD_FUSED_NN", "1") != "0"
-FUSED_TOKEN_GLUE = os.environ.get("BBD_FUSED_TOKEN_GLUE", "1") != "0"   # MonoViT: residual + DropPath + LayerNorm passes
+FUSED_NN = switch("BBD_FUSED_NN")     # 0: the encoder / decoder glue (pad, pool, bias + ELU, heads) back to the stock ATen kernels
+FUSED_TOKEN_GLUE = switch("BBD_FUSED_TOKEN_GLUE")   # MonoViT: residual + DropPath + LayerNorm passes
 
 
 class KernelTimer:
@@ -378,7 +395,7 @@ def combine_losses(loss_sum, smooths, n_px, smoothness, scales, num_scales):
 
 
 # ---------------------------------------------------------------------------- pose composition
-FUSED_POSE_COMPOSE = os.environ.get("BBD_FUSED_POSE_COMPOSE", "1") != "0"
+FUSED_POSE_COMPOSE = switch("BBD_FUSED_POSE_COMPOSE")
 
 
 class ComposeTable:
@@ -1080,6 +1097,7 @@ def factor_attention(qkv, convv, heads, scale, backend=None):
 
 
 def factor_attention_supported(C, heads, backend=None):
+    """The library's limits only (`bbd_factor_att_supported`): no switch, no tensor kind - `mpvit._hip_tokens` has those."""
     return bool((backend or default_backend()).lib.factor_att_supported(C, C // heads))
 
 
@@ -1176,12 +1194,13 @@ class _LinearTokens(torch.autograd.Function):
 
 def linear_tokens(x, linear, backend=None):
     """`linear(x)` for an nn.Linear on GPU fp32 tokens whose output width is a multiple of 4 (else the module itself)."""
-    if not (x.is_cuda and x.dtype == torch.float32 and FUSED_TOKEN_GLUE and linear.out_features % 4 == 0):
+    if not (hip_fp32(x) and FUSED_TOKEN_GLUE and linear.out_features % 4 == 0):
         return linear(x)
     return _LinearTokens.apply(x, linear.weight, linear.bias, backend or default_backend())
 
 
 def token_glue_supported(x, backend=None):
+    """The library's limits only (include/bbd_hip.h:1265, `bbd_token_ln_supported`): no switch, no tensor kind."""
     return x.dim() == 3 and bool((backend or default_backend()).lib.token_ln_supported(x.shape[-1]))
 
 
@@ -1328,6 +1347,12 @@ class _BatchNormAct(torch.autograd.Function):
         return grad_x, grad_w, grad_b, grad_res, None, None, None, None, None, None, None
 
 
+def batch_norm_act_supported(x):
+    """Tensor kind only: `bbd_bn_act_grouped_*` takes any [N,C,H,W] (include/bbd_hip.h:1019).  Its switch is the module's
+    (`FusedBatchNorm2d.fused`, BBD_FUSED_BN), and so is the module's mode: `FusedBatchNorm2d.takes_fused_launches`."""
+    return hip_fp32(x) and x.dim() == 4
+
+
 def batch_norm_act(x, weight, bias, residual, running_mean, running_var, momentum, eps, relu, backend=None,
                    num_batches_tracked=None):
     return _BatchNormAct.apply(x, weight, bias, residual, running_mean, running_var, num_batches_tracked, momentum,
@@ -1360,6 +1385,13 @@ def reflect_pad1(x, backend=None):
     return _ReflectPad1.apply(x, backend or default_backend())
 
 
+def reflect_pad1_supported(x):
+    """Switch (FUSED_NN), tensor kind and the limits of `bbd_reflect_pad1_*`: H, W >= 2 and at most MAX_PLANES planes
+    (the argument check of `bbd_reflect_pad1_fwd` in csrc/bbd_nn.hip; include/bbd_hip.h:1061 declares the call and is silent on them)."""
+    return (FUSED_NN and hip_fp32(x) and x.dim() == 4 and min(x.shape[2:]) >= 2
+            and x.shape[0] * x.shape[1] <= MAX_PLANES)
+
+
 class _MaxPool3s2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, backend):
@@ -1389,16 +1421,30 @@ def maxpool3s2(x, backend=None):
     return _MaxPool3s2.apply(x, backend or default_backend())
 
 
+def maxpool3s2_supported(x):
+    """Switch (FUSED_NN), tensor kind and the limit of `bbd_maxpool3s2_*`: at most MAX_PLANES planes, any H, W >= 1
+    (the argument check of `bbd_maxpool3s2_fwd` in csrc/bbd_nn.hip; include/bbd_hip.h:1063 declares the call and is silent on it)."""
+    return FUSED_NN and hip_fp32(x) and x.dim() == 4 and x.shape[0] * x.shape[1] <= MAX_PLANES
+
+
 # ---------------------------------------------------------------------------- encoder stem: bn1 + ReLU + max-pool
-FUSED_STEM = os.environ.get("BBD_FUSED_STEM", "1") != "0"   # 0: batch_norm_act then maxpool3s2, as before (A/B runs)
+FUSED_STEM = switch("BBD_FUSED_STEM")   # 0: batch_norm_act then maxpool3s2, as before (A/B runs)
 
 
 def stem_supported(x, rows):
     """Does `bbd_stem_*` take activation `x` [N,C,H,W] whose largest call group has `rows` samples?  (The library's own
-    condition: the two-launch BatchNorm form and rows of whole float4s; it refuses everything else.)"""
+    condition: the two-launch BatchNorm form and rows of whole float4s; it refuses everything else.)
+    Limits and dtype only (include/bbd_hip.h:1076): no switch, no device - `stem_routed` adds those."""
     return (x.dim() == 4 and x.dtype == torch.float32 and x.shape[3] % 4 == 0 and x.shape[2] >= 1
-            and 1 <= rows <= x.shape[0] and x.shape[1] <= 65535
+            and 1 <= rows <= x.shape[0] and x.shape[1] <= MAX_PLANES
             and rows * x.shape[2] * x.shape[3] > _lib.STEM_MIN_ELEMS)
+
+
+def stem_routed(x):
+    """Switches (FUSED_STEM, FUSED_NN), tensor kind and limits: the stem stands for `batch_norm_act` + `maxpool3s2`, so it
+    takes what the pool takes and `stem_supported` accepts for the active call groups.  The BatchNorm module's own
+    switch and mode are left to the caller (`FusedBatchNorm2d.takes_fused_launches`)."""
+    return FUSED_STEM and maxpool3s2_supported(x) and stem_supported(x, call_groups(x.shape[0]).biggest)
 
 
 class _StemBnReluPool(torch.autograd.Function):
@@ -1486,9 +1532,9 @@ def upcat_pad(x, skip=None, backend=None):
 
 
 def upcat_pad_supported(x, skip):
+    """Switch (FUSED_NN), tensor kind and the plane limit of `bbd_upcat_pad1_*` (include/bbd_hip.h:1139)."""
     n_planes = x.shape[0] * (x.shape[1] + (skip.shape[1] if skip is not None else 0))
-    return (FUSED_NN and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and n_planes <= 65535
-            and (skip is None or (skip.is_cuda and skip.dtype == torch.float32)))
+    return FUSED_NN and hip_fp32(x, skip) and x.dim() == 4 and n_planes <= MAX_PLANES
 
 
 class _BiasELU(torch.autograd.Function):
@@ -1523,9 +1569,17 @@ def bias_elu_(conv_out, bias, backend=None):
     return _BiasELU.apply(conv_out, bias, backend or default_backend())
 
 
+def bias_elu_supported(x, border=0):
+    """Switch (FUSED_NN), tensor kind and the limit of `bbd_bias_elu_*` (include/bbd_hip.h:1140: planes of whole float4s).
+    `x` [N,C,H,W]: the input of the 3x3 convolution whose output `bias_elu_` is to take, with `border` pixels of padding
+    on it already (the output has x's kind and its size without them).  A bias, and a contiguous convolution output, are
+    left to the caller (`layers.ConvBlock`)."""
+    return FUSED_NN and hip_fp32(x) and ((x.shape[2] - 2 * border) * (x.shape[3] - 2 * border)) % 4 == 0
+
+
 # ---------------------------------------------------------------------------- decoder glue with bias + ELU inside
 # 0: upcat_pad / bias_elu_ / reflect_pad1 one after the other, as before (A/B runs)
-FUSED_DECODER_GLUE = os.environ.get("BBD_FUSED_DECODER_GLUE", "1") != "0"
+FUSED_DECODER_GLUE = switch("BBD_FUSED_DECODER_GLUE")
 
 
 def _glue_scratch(channels, N, rows, device):
@@ -1535,25 +1589,27 @@ def _glue_scratch(channels, N, rows, device):
 
 
 def _glue_tensor(t):
-    return t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+    return hip_fp32(t) and t.is_contiguous()
 
 
 def upcat_pad_act_supported(z, bias, skip):
-    """Does `bbd_upcat_pad_act_*` take the convolution output `z` [N,C1,h,w] with `skip` [N,C2,2h,2w] or None?"""
+    """Does `bbd_upcat_pad_act_*` take the convolution output `z` [N,C1,h,w] with `skip` [N,C2,2h,2w] or None?  Tensor kind
+    (contiguous) and limits (include/bbd_hip.h:1164); no switch: `DepthDecoder` asks FUSED_DECODER_GLUE and FUSED_NN first."""
     if z.dim() != 4 or bias is None or not (_glue_tensor(z) and _glue_tensor(bias)):
         return False
     N, C1, h, w = z.shape
     if skip is not None and not (_glue_tensor(skip) and skip.shape == (N, skip.shape[1], 2 * h, 2 * w)):
         return False
-    return h >= 1 and w >= 1 and 1 <= N * (C1 + (skip.shape[1] if skip is not None else 0)) <= 65535
+    return h >= 1 and w >= 1 and 1 <= N * (C1 + (skip.shape[1] if skip is not None else 0)) <= MAX_PLANES
 
 
 def bias_elu_pad_supported(z, bias):
-    """Does `bbd_bias_elu_pad_*` take the convolution output `z` [N,C,H,W]?"""
+    """Does `bbd_bias_elu_pad_*` take the convolution output `z` [N,C,H,W]?  Tensor kind (contiguous) and limits
+    (include/bbd_hip.h:1164); no switch, as `upcat_pad_act_supported`."""
     if z.dim() != 4 or bias is None or not (_glue_tensor(z) and _glue_tensor(bias)):
         return False
     N, C, H, W = z.shape
-    return H >= 2 and W >= 2 and 1 <= N * C <= 65535
+    return H >= 2 and W >= 2 and 1 <= N * C <= MAX_PLANES
 
 
 class _UpCatPadAct(torch.autograd.Function):
@@ -1637,7 +1693,7 @@ def bias_elu_pad(conv_out, bias, backend=None):
 
 # ---------------------------------------------------------------------------- ConvBlock weight gradients from NCHW
 # 0: every weight gradient stays with MIOpen, as before (A/B runs)
-FUSED_WGRAD = os.environ.get("BBD_FUSED_WGRAD", "1") != "0"
+FUSED_WGRAD = switch("BBD_FUSED_WGRAD")
 
 # (C, K, H, W) of a ConvBlock convolution - input channels, output channels, output size - whose weight gradient
 # `bbd_conv3x3_wgrad` takes, at any batch size.  A row is here because tools/wgrad_bench.py measured the call's slowest
@@ -1651,7 +1707,7 @@ WGRAD_ROUTES = {
 
 def conv3x3_wgrad_shape(xp, w):
     """(N, C, K, H, W) of `bbd_conv3x3_wgrad` for the padded input `xp` and the weight `w`, or None where the call does
-    not take them: contiguous fp32 GPU tensors, a [K,C,3,3] weight."""
+    not take them: contiguous fp32 GPU tensors, a [K,C,3,3] weight.  Tensor kind and shape; `_routed` adds the rest."""
     if not (xp.dim() == 4 and w.dim() == 4 and _glue_tensor(xp) and _glue_tensor(w)):
         return None
     N, C, Hp, Wp = xp.shape
@@ -1662,7 +1718,7 @@ def conv3x3_wgrad_shape(xp, w):
 
 def conv3x3_wgrad_routed(xp, w, backend=None):
     """Does the weight gradient of `F.conv2d(xp, w)` go to `bbd_conv3x3_wgrad`?  Only for the measured rows of
-    WGRAD_ROUTES, and never with BBD_FUSED_WGRAD=0 or BBD_FUSED_NN=0."""
+    WGRAD_ROUTES, and never with BBD_FUSED_WGRAD=0 or BBD_FUSED_NN=0.  Switches, tensor kind and the library's limits."""
     if not (FUSED_WGRAD and FUSED_NN):
         return False
     shape = conv3x3_wgrad_shape(xp, w)
@@ -1718,7 +1774,7 @@ def conv3x3_valid(xp, w, backend=None):
 
 # ---------------------------------------------------------------------------- up-sample + pad + 3x3 conv, sub-pixel form
 # 0: the finest decoder level keeps upcat_pad_act + convolution, as before (A/B runs)
-FUSED_UP2CONV = os.environ.get("BBD_FUSED_UP2CONV", "1") != "0"
+FUSED_UP2CONV = switch("BBD_FUSED_UP2CONV")
 
 # (C, K, h, w) - channels in and out, size of the low-resolution map - of a decoder level without a skip connection whose
 # second ConvBlock `bbd_up2conv3x3_*` takes, at any batch size.  A row is here because tools/up2conv_bench.py measured the
@@ -1731,7 +1787,7 @@ UP2CONV_ROUTES = {
 
 def up2_conv3x3_shape(z, bias, weight):
     """(N, C, K, h, w) of `bbd_up2conv3x3_*` for the convolution output `z`, its bias and the next 3x3 weight, or None
-    where the calls do not take them: contiguous fp32 GPU tensors, a [K,C,3,3] weight."""
+    where the calls do not take them: contiguous fp32 GPU tensors, a [K,C,3,3] weight.  Tensor kind and shape only."""
     if bias is None or not (z.dim() == 4 and weight.dim() == 4 and _glue_tensor(z) and _glue_tensor(bias) and _glue_tensor(weight)):
         return None
     N, C, h, w = z.shape
@@ -1742,7 +1798,8 @@ def up2_conv3x3_shape(z, bias, weight):
 
 def up2_conv3x3_routed(z, bias, weight, backend=None):
     """Does `conv2d(upcat_pad_act(z, bias), weight)` go to `bbd_up2conv3x3_*`?  Only for the measured rows of
-    UP2CONV_ROUTES, and never with BBD_FUSED_UP2CONV=0, BBD_FUSED_NN=0 or BBD_FUSED_DECODER_GLUE=0."""
+    UP2CONV_ROUTES, and never with BBD_FUSED_UP2CONV=0, BBD_FUSED_NN=0 or BBD_FUSED_DECODER_GLUE=0.  Switches, tensor kind
+    and the library's limits."""
     if not (FUSED_UP2CONV and FUSED_NN and FUSED_DECODER_GLUE):
         return False
     shape = up2_conv3x3_shape(z, bias, weight)
@@ -1807,6 +1864,17 @@ def up2_conv3x3(z, bias, weight, backend=None):
 
 
 # ---------------------------------------------------------------------------- disparity head Conv3x3(C -> 1)
+DISP_HEAD_MAX_CHANNELS = 256        # DC_MAXC of csrc/bbd_nn.hip (the weights' shared-memory copy); not in the header
+
+
+def disp_head_supported(x, channels):
+    """`dispconv` and `disp_head` alike: switch (FUSED_NN), tensor kind and the limits of `bbd_dispconv_*` / `bbd_disp_head_*`
+    for an `x` of `channels` channels: at most DISP_HEAD_MAX_CHANNELS, H and W >= 2 (the argument checks of the dispconv launchers and DC_MAXC in csrc/bbd_nn.hip; include/bbd_hip.h:1103
+    declares the calls and is silent on them; a batch above MAX_PLANES is refused there, with an error, not here).  That the
+    layer has ONE output channel and a reflection border is the module's to say (`layers.Conv3x3`)."""
+    return FUSED_NN and hip_fp32(x) and channels <= DISP_HEAD_MAX_CHANNELS and min(x.shape[2:]) >= 2
+
+
 class _DispConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, backend):
