@@ -29,6 +29,8 @@ WGRAD_HELPERS, _ = _abi.read_header(os.path.join(os.path.dirname(_abi.HEADER), "
 UP2CONV_HELPERS, _ = _abi.read_header(os.path.join(os.path.dirname(_abi.HEADER), "bbd_up2conv.h"))
 # ... and the scratch query of bbd_sgm_hints (include/bbd_sgm.h)
 SGM_HELPERS, _ = _abi.read_header(os.path.join(os.path.dirname(_abi.HEADER), "bbd_sgm.h"))
+# ... and the two queries of bbd_stem_conv7s2_fwd / _wgrad (include/bbd_stemconv.h)
+STEMCONV_HELPERS, _ = _abi.read_header(os.path.join(os.path.dirname(_abi.HEADER), "bbd_stemconv.h"))
 
 
 class HipLibrary:
@@ -48,7 +50,8 @@ class HipLibrary:
                 # the host-side helpers, under their ABI name minus `bbd_`: lib.num_tiles(H, W), lib.map_state_bytes(T);
                 # one without parameters is a constant of the build and is bound as its value: lib.tile_w, lib.smooth_chunks
                 setattr(self, name[len("bbd_"):], fn if proto.params else fn())
-        for name, proto in list(WGRAD_HELPERS.items()) + list(UP2CONV_HELPERS.items()) + list(SGM_HELPERS.items()):
+        for name, proto in list(WGRAD_HELPERS.items()) + list(UP2CONV_HELPERS.items()) + list(SGM_HELPERS.items()) \
+                + list(STEMCONV_HELPERS.items()):
             fn = getattr(self._dll, name)
             fn.argtypes, fn.restype = [ctype for ctype, _ in proto.params], proto.restype
             setattr(self, name[len("bbd_"):], fn)

@@ -160,12 +160,21 @@ class ResnetEncoder(nn.Module):
         f0 = bn(x, relu=True)
         return (f0 if self.stem_feature else None), e.maxpool(f0)
 
+    def _conv1(self, image, normalized):
+        """conv1 of the normalised image: `ops.stem_conv` where a direction of it is routed (it normalises on the way in),
+        else the normalisation and the module's own convolution."""
+        conv = self.encoder.conv1
+        if (type(conv) is nn.Conv2d and conv.bias is None and conv.stride == (2, 2) and conv.padding == (3, 3)
+                and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros"
+                and any(ops.stem_conv_routed(image, conv.weight, d) for d in ("fwd", "wgrad"))):
+            return ops.stem_conv(image, conv.weight, normalize=not normalized)
+        return conv(image if normalized else (image - 0.45) / 0.225)
+
     def forward(self, input_image, normalized=False):
         """`normalized`: the caller hands in `(image - 0.45) / 0.225` already (the pooled step's pair gather does it in the
         same pass, `ops.gather_pairs`)."""
         e = self.encoder
-        x = input_image if normalized else (input_image - 0.45) / 0.225
-        f0, pooled = self._stem(e.conv1(x))
+        f0, pooled = self._stem(self._conv1(input_image, normalized))
         f1 = e.layer1(pooled)
         f2 = e.layer2(f1)
         f3 = e.layer3(f2)

@@ -1863,6 +1863,135 @@ def up2_conv3x3(z, bias, weight, backend=None):
     return _Up2Conv3x3.apply(z, bias, weight, backend or default_backend())
 
 
+# ---------------------------------------------------------------------------- encoder stems: conv1, 7x7 stride 2
+# 0: both stems' conv1 stay with MIOpen in both directions, as before (A/B runs)
+FUSED_STEMCONV = switch("BBD_FUSED_STEMCONV")
+
+# (C, H, W, direction) - input channels and input size of an encoder's conv1, "fwd" or "wgrad" - that goes to
+# `bbd_stem_conv7s2_*`, at any batch size.  A row is here because tools/stemconv_bench.py measured the new call's slowest
+# repeat faster than MIOpen's fastest, at batch 12 (C = 3) or 24 (C = 6) (profiles/stem_conv/stemconv_bench.json); every
+# other shape and direction stays with MIOpen, those the kernels support but were not measured on included.
+STEMCONV_ROUTES = {
+    (3, 192, 640, "fwd"),       # depth encoder, N = 12: 100 us against MIOpen's 171 us (medians)
+    (3, 192, 640, "wgrad"),     # 143 us against 179 us
+    (6, 192, 640, "fwd"),       # pose encoder, N = 24: 359 us against 460 us
+}                               # not here: (6, 192, 640, "wgrad"), 419 / 440 / 467 us against MIOpen's 453 / 471 / 506 us
+#                                 in one run (slowest repeat above MIOpen's fastest), 413 / 416 / 427 against 452 / 456 /
+#                                 471 in a second one (the committed json): passes the rule in one run of two
+NORMALIZE_MEAN, NORMALIZE_STD = 0.45, 0.225        # the encoder's input normalisation, folded in by `normalize=True`
+
+
+def stem_conv_shape(x, w):
+    """(N, C, K, H, W, R, S) of `bbd_stem_conv7s2_*` for the image `x` and the weight `w`, or None where the calls cannot
+    take them: contiguous fp32 GPU tensors, a [K,C,R,S] weight on x's channels, nothing empty.  Tensor kind and shape only."""
+    if not (x.dim() == 4 and w.dim() == 4 and _glue_tensor(x) and _glue_tensor(w)):
+        return None
+    N, C, H, W = x.shape
+    K, Cw, R, S = w.shape
+    if Cw != C or min(N, C, H, W, K, R, S) < 1:
+        return None
+    return N, C, K, H, W, R, S
+
+
+def stem_conv_routed(x, w, direction, backend=None):
+    """Does `direction` ("fwd" or "wgrad") of `conv2d(x, w, stride 2, pad 3)` go to `bbd_stem_conv7s2_*`?  Only for the
+    measured rows of STEMCONV_ROUTES, and never with BBD_FUSED_STEMCONV=0 or BBD_FUSED_NN=0.  Switches, tensor kind and
+    the library's limits."""
+    if not (FUSED_STEMCONV and FUSED_NN):
+        return False
+    shape = stem_conv_shape(x, w)
+    if shape is None or (shape[1], shape[3], shape[4], direction) not in STEMCONV_ROUTES:
+        return False
+    return bool((backend or default_backend()).lib.stem_conv7s2_supported(*shape))
+
+
+def _stem_conv_args(x, w, backend):
+    backend._check(x, w)
+    shape = stem_conv_shape(x, w)
+    if shape is None or not backend.lib.stem_conv7s2_supported(*shape):
+        raise _lib.BbdError("bbd_stem_conv7s2 does not take x %s, w %s" % (tuple(x.shape), tuple(w.shape)))
+    return shape
+
+
+def stem_conv_fwd(x, w, normalize=False, backend=None):
+    """conv2d(x', w, stride 2, pad 3) [N,64,Ho,Wo] in one launch; x' = (x - 0.45) / 0.225 with `normalize`, else x."""
+    backend = backend or default_backend()
+    N, C, K, H, W, _, _ = _stem_conv_args(x, w, backend)
+    out = torch.empty(N, K, (H + 1) // 2, (W + 1) // 2, device=x.device, dtype=torch.float32)
+    backend.run("bbd_stem_conv7s2_fwd", x, ptr(x), ptr(w), ptr(out), N, C, K, H, W, int(bool(normalize)))
+    return out
+
+
+def stem_conv_wgrad(x, w, grad_out, normalize=False, backend=None):
+    """grad_w [64,C,7,7] of that convolution from x and grad_out [N,64,Ho,Wo] (`w` gives the shape only): two launches,
+    no atomics, scratch from the torch allocator."""
+    backend = backend or default_backend()
+    shape = _stem_conv_args(x, w, backend)
+    N, C, K, H, W, _, _ = shape
+    backend._check(grad_out)
+    grad_out = grad_out.contiguous()
+    assert grad_out.shape == (N, K, (H + 1) // 2, (W + 1) // 2) and grad_out.dtype == torch.float32
+    doubles = backend.lib.stem_conv7s2_wgrad_scratch_doubles(*shape)
+    scratch = torch.empty(doubles, device=x.device, dtype=torch.float64)
+    grad_w = torch.empty(K, C, 7, 7, device=x.device, dtype=torch.float32)
+    backend.run("bbd_stem_conv7s2_wgrad", x, ptr(x), ptr(grad_out), ptr(grad_w), ptr(scratch), doubles, N, C, K, H, W,
+                int(bool(normalize)))
+    return grad_w
+
+
+def _normalized(x):
+    return (x - NORMALIZE_MEAN) / NORMALIZE_STD
+
+
+class _StemConv(torch.autograd.Function):
+    """`F.conv2d(x', w, None, 2, 3)` of an encoder's conv1, x' = the normalised image with `normalize`.  Forward and weight
+    gradient go to `bbd_stem_conv7s2_*` or to MIOpen independently (`fwd`, `wgrad`); MIOpen's side is the problem it has
+    without this function.  An input that requires grad gets MIOpen's data gradient.  With `normalize`, only a function
+    routed in BOTH directions never forms x' with torch ops: an unrouted forward forms it as before, and an unrouted weight
+    gradient behind a routed forward forms it in the backward (the raw image is what is saved)."""
+
+    @staticmethod
+    def forward(ctx, x, w, normalize, fwd, wgrad, backend):
+        ctx.normalize, ctx.wgrad, ctx.backend = normalize, wgrad, backend
+        if fwd:
+            out = stem_conv_fwd(x, w, normalize, backend)
+            ctx.save_for_backward(x, w)
+            ctx.raw = True
+        else:
+            xn = _normalized(x) if normalize else x
+            out = torch.nn.functional.conv2d(xn, w, None, 2, 3)
+            ctx.raw = wgrad                                      # the routed weight gradient re-forms x' from x itself
+            ctx.save_for_backward(x if wgrad else xn, w)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, w = ctx.saved_tensors
+        grad_x = grad_w = None
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if need_w and ctx.wgrad:
+            grad_w = stem_conv_wgrad(x, w, grad_out, ctx.normalize, ctx.backend)
+            need_w = False
+        if need_x or need_w:
+            xn = _normalized(x) if (ctx.normalize and ctx.raw) else x
+            gx, gw, _ = torch.ops.aten.convolution_backward(grad_out, xn, w, None, [2, 2], [3, 3], [1, 1], False, [0, 0], 1,
+                                                            [need_x, need_w, False])
+            if need_x:
+                grad_x = gx / NORMALIZE_STD if ctx.normalize else gx
+            if need_w:
+                grad_w = gw
+        return grad_x, grad_w, None, None, None, None
+
+
+def stem_conv(x, w, normalize=False, backend=None, fwd=None, wgrad=None):
+    """An encoder's conv1 on `x` (`normalize`: on `(x - 0.45) / 0.225`), each direction where `stem_conv_routed` sends it
+    (`fwd` / `wgrad` override the table: the tests and tools/stemconv_bench.py)."""
+    backend = backend or default_backend()
+    fwd = stem_conv_routed(x, w, "fwd", backend) if fwd is None else fwd
+    wgrad = stem_conv_routed(x, w, "wgrad", backend) if wgrad is None else wgrad
+    return _StemConv.apply(x, w, bool(normalize), bool(fwd), bool(wgrad), backend)
+
+
 # ---------------------------------------------------------------------------- disparity head Conv3x3(C -> 1)
 DISP_HEAD_MAX_CHANNELS = 256        # DC_MAXC of csrc/bbd_nn.hip (the weights' shared-memory copy); not in the header
 

@@ -61,8 +61,9 @@ extern "C" {
  * 25 = bbd_geo_fwd / bbd_geo_bwd (the geometry-consistency loss for training, forward and backward);
  * 26 = bbd_up2conv3x3_fwd / _bwd (the decoder's finest up-sample + pad + 3x3 convolution in sub-pixel form);
  * 27 = bbd_sgm_hints (semi-global stereo matching: proxy disparities for --depth_hints);
- * 28 = bbd_depth_metrics_affine (depth evaluation under a per-image least-squares scale and shift). */
-#define BBD_ABI_VERSION 28
+ * 28 = bbd_depth_metrics_affine (depth evaluation under a per-image least-squares scale and shift);
+ * 29 = bbd_stem_conv7s2_fwd / _wgrad (the encoder stems' 7x7 stride-2 convolution and its weight gradient). */
+#define BBD_ABI_VERSION 29
 
 /* Source frames live in separate tensors, one per frame id (inputs[("color", f, 0)],
  * trainer.py:428).  A "slot" indexes a host array of their base pointers. */
@@ -1220,6 +1221,33 @@ int bbd_up2conv3x3_fwd(const float* z, const float* bias, const float* w, float*
 int bbd_up2conv3x3_bwd(const float* grad_out, const float* z, const float* bias, const float* w, float* grad_z,
                        float* grad_bias, double* scratch, int scratch_doubles, int N, int C, int K, int h, int w_,
                        void* stream);
+
+/* The encoder stems' conv1 - 7x7, stride 2, pad 3, C = 3 or 6 input channels, K = 64 output channels, no bias - and its
+ * weight gradient, straight from the NCHW tensors.  All tensors contiguous fp32; Ho = (H + 1) / 2,
+ * Wo = (W + 1) / 2:
+ *   bbd_stem_conv7s2_fwd   : out [N, 64, Ho, Wo] = conv2d(x' [N, C, H, W], w [64, C, 7, 7], stride 2, pad 3), where
+ *                            x' = x, or with normalize != 0 the encoder's (x - 0.45) / 0.225 evaluated as bbd_gather_pairs
+ *                            evaluates it (subtract, multiply by the float reciprocal); the zero border pads x'.
+ *   bbd_stem_conv7s2_wgrad : grad_w [64, C, 7, 7] (written, not accumulated) = sum over (n, oy, ox) of
+ *                            grad_out[n][k][oy][ox] * x'[n][c][2 oy + r - 3][2 ox + s - 3], x' re-formed from x by the
+ *                            same flag.  scratch holds bbd_stem_conv7s2_wgrad_scratch_doubles(...) doubles and
+ *                            scratch_doubles says how many it has; none is read before the call wrote it.
+ * Numerics: v_mfma_f32_16x16x4_f32 is an exact fp32 fma chain; no atomics and nothing zeroed first, so two calls give
+ * equal bits and every element of every output is written.  Forward: one chain per input channel over its 49 taps
+ * (padding taps carry weight zero and add exactly nothing), the C chains added in fp32 - fewer roundings than one chain
+ * over all C * 49 taps, so |out - exact| <= (P + 1) * 2^-24 * sum |w| |x'| with P = 148 (C = 3) or 296 (C = 6).  Weight gradient: every fp32 accumulator takes at most BBD_WGRAD_RUN products and is
+ * then added to a double; doubles are added in a fixed order (per lane, then over the workgroups by a second launch):
+ * |grad_w - exact| <= (BBD_WGRAD_RUN + 1) * 2^-24 * sum |grad_out| |x'|.
+ * x must be finite: the zero taps that pad the reduction and, in the weight gradient, the pixels past the last row or
+ * column of out multiply an exact zero by a staged value of x, so an Inf or NaN in x can reach elements that conv2d would
+ * leave finite.
+ * The two host-side queries are declared in include/bbd_stemconv.h.  A shape bbd_stem_conv7s2_supported refuses -
+ * K != 64, C not 3 or 6, N, H or W below 1, a tensor of 2^31 elements or more - a NULL pointer or a scratch that is too
+ * small return BBD_E_BADARG and launch nothing. */
+int bbd_stem_conv7s2_fwd(const float* x, const float* w, float* out, int N, int C, int K, int H, int W, int normalize,
+                         void* stream);
+int bbd_stem_conv7s2_wgrad(const float* x, const float* grad_out, float* grad_w, double* scratch, int scratch_doubles,
+                           int N, int C, int K, int H, int W, int normalize, void* stream);
 
 /* ---- MonoViT encoder (BASELINE configs[4]): depth-wise convolution on token-layout activations ----------
  * The position encodings of the reference's MPViT (networksvit/mpvit.py:240-330: ConvPosEnc, ConvRelPosEnc)
