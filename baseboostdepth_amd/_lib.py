@@ -31,6 +31,8 @@ UP2CONV_HELPERS, _ = _abi.read_header(os.path.join(os.path.dirname(_abi.HEADER),
 SGM_HELPERS, _ = _abi.read_header(os.path.join(os.path.dirname(_abi.HEADER), "bbd_sgm.h"))
 # ... and the two queries of bbd_stem_conv7s2_fwd / _wgrad (include/bbd_stemconv.h)
 STEMCONV_HELPERS, _ = _abi.read_header(os.path.join(os.path.dirname(_abi.HEADER), "bbd_stemconv.h"))
+# ... and the two queries of bbd_conv1x1s2_fwd / _bwd_data / _wgrad (include/bbd_conv1x1.h)
+CONV1X1_HELPERS, _ = _abi.read_header(os.path.join(os.path.dirname(_abi.HEADER), "bbd_conv1x1.h"))
 
 
 class HipLibrary:
@@ -51,7 +53,7 @@ class HipLibrary:
                 # one without parameters is a constant of the build and is bound as its value: lib.tile_w, lib.smooth_chunks
                 setattr(self, name[len("bbd_"):], fn if proto.params else fn())
         for name, proto in list(WGRAD_HELPERS.items()) + list(UP2CONV_HELPERS.items()) + list(SGM_HELPERS.items()) \
-                + list(STEMCONV_HELPERS.items()):
+                + list(STEMCONV_HELPERS.items()) + list(CONV1X1_HELPERS.items()):
             fn = getattr(self._dll, name)
             fn.argtypes, fn.restype = [ctype for ctype, _ in proto.params], proto.restype
             setattr(self, name[len("bbd_"):], fn)

@@ -47,13 +47,14 @@ SRCS = _here("""
     bbd_sgm.hip
     bbd_align.hip
     bbd_stemconv.hip
+    bbd_conv1x1.hip
 """)
 OUT = os.path.join(HERE, "libbbd_hip.so")
 # every header of this directory: one that is forgotten here would leave a stale library behind an edit
 DEPS = SRCS + [os.path.abspath(__file__)] + sorted(glob.glob(os.path.join(HERE, "*.h"))) + [
     os.path.join(HERE, "..", "..", "include", "bbd_hip.h"), os.path.join(HERE, "..", "..", "include", "bbd_wgrad.h"),
     os.path.join(HERE, "..", "..", "include", "bbd_up2conv.h"), os.path.join(HERE, "..", "..", "include", "bbd_sgm.h"),
-    os.path.join(HERE, "..", "..", "include", "bbd_stemconv.h")]
+    os.path.join(HERE, "..", "..", "include", "bbd_stemconv.h"), os.path.join(HERE, "..", "..", "include", "bbd_conv1x1.h")]
 # -fno-slp-vectorize: hipcc otherwise SLP-packs neighbouring scalar fp32 adds / multiplies into v_pk_add/mul_f32 and
 # pays for it in v_mov register shuffles (129 moves in the forward's SSIM phase): measured forward 0.222 -> 0.208 ms,
 # identity 0.0365 -> 0.0340 ms, backward 0.348 -> 0.343 ms (profiles/r02/slp_variants.txt).  Same operations, same bits.

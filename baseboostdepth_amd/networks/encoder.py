@@ -50,6 +50,13 @@ class MaxPool3s2(nn.MaxPool2d):
         return super().forward(x)
 
 
+def _plain_conv(conv, kernel, stride, padding):
+    """Is `conv` a bias-free `nn.Conv2d` of that square kernel, stride and zero padding, dilation 1, groups 1?"""
+    return (type(conv) is nn.Conv2d and conv.bias is None and conv.kernel_size == (kernel, kernel)
+            and conv.stride == (stride, stride) and conv.padding == (padding, padding) and conv.dilation == (1, 1)
+            and conv.groups == 1 and conv.padding_mode == "zeros")
+
+
 class BasicBlock(nn.Module):
     expansion = 1
 
@@ -62,9 +69,30 @@ class BasicBlock(nn.Module):
         self.bn2 = FusedBatchNorm2d(planes)
         self.downsample = downsample
 
+    def _entry(self, x):
+        """(conv1(x), the shortcut of x).  A down-sampling block whose shortcut convolution is routed in some direction
+        sends it through `ops.conv1x1_s2`, or where `ops.block_entry_routed` says so both convolutions through `ops.block_entry`
+        (one node: the shortcut's gradient is added into conv1's in place); `downsample.1` follows as before."""
+        ds = self.downsample
+        if ds is None:
+            return self.conv1(x), x
+        short = ds[0] if isinstance(ds, nn.Sequential) and len(ds) > 0 else None
+        if (_plain_conv(short, 1, 2, 0)
+                and any(ops.conv1x1s2_routed(x, short.weight, d) for d in ("fwd", "dgrad", "wgrad"))):
+            if _plain_conv(self.conv1, 3, 2, 1) and ops.block_entry_routed(x, short.weight):
+                out, identity = ops.block_entry(x, self.conv1.weight, short.weight)
+            else:
+                identity = ops.conv1x1_s2(x, short.weight)
+                out = self.conv1(x)
+            for module in list(ds)[1:]:
+                identity = module(identity)
+            return out, identity
+        identity = ds(x)
+        return self.conv1(x), identity
+
     def forward(self, x):
-        identity = x if self.downsample is None else self.downsample(x)
-        out = self.bn1(self.conv1(x), relu=True)
+        out, identity = self._entry(x)
+        out = self.bn1(out, relu=True)
         return self.bn2(self.conv2(out), residual=identity, relu=True)
 
 

@@ -1992,6 +1992,210 @@ def stem_conv(x, w, normalize=False, backend=None, fwd=None, wgrad=None):
     return _StemConv.apply(x, w, bool(normalize), bool(fwd), bool(wgrad), backend)
 
 
+# ---------------------------------------------------------------------------- ResNet shortcuts: 1x1, stride 2
+# 0: every shortcut convolution stays with MIOpen in all three directions and BasicBlock runs its two entry convolutions
+# as separate autograd nodes, as before (A/B runs)
+FUSED_CONV1X1 = switch("BBD_FUSED_CONV1X1")
+
+# (C, K, H, W, direction) - channels and INPUT size of a `layer{2,3,4}.0.downsample.0`, "fwd", "dgrad" or "wgrad" - that
+# goes to `bbd_conv1x1s2_*`, at any batch size.  A row is here because tools/conv1x1_bench.py measured the new call's
+# slowest repeat faster than MIOpen's fastest at batch 12 AND at batch 24 (the depth and the pose encoder share the
+# shapes; profiles/conv1x1/conv1x1_bench.json); every other shape and direction stays with MIOpen, those the kernels
+# support but were not measured on included.
+CONV1X1_ROUTES = {              # whole call, medians in us, new against MIOpen, at N = 12 / N = 24
+    (64, 128, 48, 160, "fwd"),      # layer2: 20 against 39 / 28 against 50
+    (64, 128, 48, 160, "dgrad"),    # 22 against 48 / 26 against 62
+    (64, 128, 48, 160, "wgrad"),    # 36 against 43 / 47 against 58
+    (128, 256, 24, 80, "fwd"),      # layer3: 21 against 33 / 26 against 45
+    (128, 256, 24, 80, "dgrad"),    # 24 against 43 / 28 against 52
+    (256, 512, 12, 40, "fwd"),      # layer4: 22 against 31 / 29 against 41
+    (256, 512, 12, 40, "dgrad"),    # 33 against 39 / 34 against 45
+}                                   # not here: layer3 "wgrad" (34 against 40 at N = 12, but 45.3 / 46.0 / 49.2 against MIOpen's
+#                                     46.6 / 46.8 / 48.9 at N = 24) and layer4 "wgrad" (31.2 / 32.2 / 35.1 against 33.6 / 34.8 / 36.2
+#                                     and 41.2 / 44.5 / 46.3 against 44.4 / 45.2 / 46.6): the slowest repeat is above MIOpen's fastest
+# (C, K, H, W) of a shortcut whose block takes `block_entry` - its two entry convolutions as one autograd node, the
+# shortcut's data gradient added into conv1's in place - where the "dgrad" row above is routed too: the shapes at which
+# tools/conv1x1_bench.py measured the joint backward faster than conv1's backward + MIOpen's shortcut gradient + the ATen
+# add, by the same rule at both batches.  Elsewhere a routed shortcut runs `conv1x1_s2` beside the module's conv1.
+BLOCK_ENTRY_ROUTES = {(64, 128, 48, 160)}      # layer2: 162 against 191 / 248 against 293 us; layers 3 and 4 did not pass
+#                                                (164.5 against 178.3 / 242.2 against 267.3 and 166.6 against 166.2 / 231.7
+#                                                against 241.7 in the medians, the ranges overlap)
+
+
+def conv1x1s2_shape(x, w):
+    """(N, C, K, H, W) of `bbd_conv1x1s2_*` for the input `x` and the weight `w`, or None where the calls cannot take
+    them: contiguous fp32 GPU tensors, a [K,C,1,1] weight on x's channels, nothing empty.  Tensor kind and shape only."""
+    if not (x.dim() == 4 and w.dim() == 4 and _glue_tensor(x) and _glue_tensor(w)):
+        return None
+    N, C, H, W = x.shape
+    K, Cw, R, S = w.shape
+    if Cw != C or (R, S) != (1, 1) or min(N, C, H, W, K) < 1:
+        return None
+    return N, C, K, H, W
+
+
+def conv1x1s2_routed(x, w, direction, backend=None):
+    """Does `direction` ("fwd", "dgrad" or "wgrad") of `conv2d(x, w, stride 2)` go to `bbd_conv1x1s2_*`?  Only for the
+    measured rows of CONV1X1_ROUTES, and never with BBD_FUSED_CONV1X1=0 or BBD_FUSED_NN=0.  Switches, tensor kind and
+    the library's limits."""
+    if not (FUSED_CONV1X1 and FUSED_NN):
+        return False
+    shape = conv1x1s2_shape(x, w)
+    if shape is None or (shape[1], shape[2], shape[3], shape[4], direction) not in CONV1X1_ROUTES:
+        return False
+    return bool((backend or default_backend()).lib.conv1x1s2_supported(*shape))
+
+
+def block_entry_routed(x, w1, backend=None):
+    """Does the block that reads `x` take `block_entry`?  The shortcut's data gradient is routed and its shape is a row of
+    BLOCK_ENTRY_ROUTES."""
+    if not conv1x1s2_routed(x, w1, "dgrad", backend):
+        return False
+    return tuple(conv1x1s2_shape(x, w1)[1:]) in BLOCK_ENTRY_ROUTES
+
+
+def _conv1x1s2_args(x_shape, w, backend, *tensors):
+    backend._check(w, *tensors)
+    N, C, H, W = x_shape
+    K = w.shape[0]
+    ok = (w.dim() == 4 and tuple(w.shape[1:]) == (C, 1, 1) and all(_glue_tensor(t) for t in (w,) + tensors)
+          and backend.lib.conv1x1s2_supported(N, C, K, H, W))
+    if not ok:
+        raise _lib.BbdError("bbd_conv1x1s2 does not take x %s, w %s" % (tuple(x_shape), tuple(w.shape)))
+    return N, C, K, H, W
+
+
+def conv1x1s2_fwd(x, w, backend=None):
+    """conv2d(x, w, stride 2) [N,K,Ho,Wo] of a [K,C,1,1] weight in one launch."""
+    backend = backend or default_backend()
+    N, C, K, H, W = _conv1x1s2_args(x.shape, w, backend, x)
+    out = torch.empty(N, K, (H + 1) // 2, (W + 1) // 2, device=x.device, dtype=torch.float32)
+    backend.run("bbd_conv1x1s2_fwd", x, ptr(x), ptr(w), ptr(out), N, C, K, H, W)
+    return out
+
+
+def conv1x1s2_bwd_data(grad_out, w, x_shape, into=None, backend=None):
+    """The data gradient [N,C,H,W] of that convolution in one launch.  `into` None: a new tensor, every element written
+    (the zeros of odd rows and columns too).  `into` a contiguous [N,C,H,W] tensor: the gradient is ADDED to its even
+    positions in place, nothing else is touched, and `into` is returned."""
+    backend = backend or default_backend()
+    grad_out = grad_out.contiguous()
+    N, C, K, H, W = _conv1x1s2_args(x_shape, w, backend, grad_out)
+    assert grad_out.shape == (N, K, (H + 1) // 2, (W + 1) // 2) and grad_out.dtype == torch.float32
+    if into is None:
+        grad_x = torch.empty(N, C, H, W, device=grad_out.device, dtype=torch.float32)
+    else:
+        backend._check(into)
+        assert tuple(into.shape) == (N, C, H, W) and _glue_tensor(into)
+        grad_x = into
+    backend.run("bbd_conv1x1s2_bwd_data", grad_out, ptr(grad_out), ptr(w), ptr(grad_x), N, C, K, H, W, int(into is not None))
+    return grad_x
+
+
+def conv1x1s2_wgrad(x, w, grad_out, backend=None):
+    """grad_w [K,C,1,1] of that convolution from x and grad_out [N,K,Ho,Wo] (`w` gives the shape only): two launches, no
+    atomics, scratch from the torch allocator."""
+    backend = backend or default_backend()
+    grad_out = grad_out.contiguous()
+    N, C, K, H, W = _conv1x1s2_args(x.shape, w, backend, x, grad_out)
+    assert grad_out.shape == (N, K, (H + 1) // 2, (W + 1) // 2) and grad_out.dtype == torch.float32
+    doubles = backend.lib.conv1x1s2_wgrad_scratch_doubles(N, C, K, H, W)
+    scratch = torch.empty(doubles, device=x.device, dtype=torch.float64)
+    grad_w = torch.empty(K, C, 1, 1, device=x.device, dtype=torch.float32)
+    backend.run("bbd_conv1x1s2_wgrad", x, ptr(x), ptr(grad_out), ptr(grad_w), ptr(scratch), doubles, N, C, K, H, W)
+    return grad_w
+
+
+def _conv_backward(grad_out, x, w, stride, padding, need_x, need_w):
+    """MIOpen's side of a bias-free convolution's backward: (grad_x, grad_w), None where not asked for."""
+    gx, gw, _ = torch.ops.aten.convolution_backward(grad_out, x, w, None, [stride, stride], [padding, padding], [1, 1],
+                                                    False, [0, 0], 1, [need_x, need_w, False])
+    return (gx if need_x else None), (gw if need_w else None)
+
+
+def _conv1x1s2_backward(ctx_dgrad, ctx_wgrad, backend, grad_out, x, w, need_x, need_w):
+    """(grad_x, grad_w) of the shortcut, each from `bbd_conv1x1s2_*` or from MIOpen."""
+    grad_x = grad_w = None
+    if need_w and ctx_wgrad:
+        grad_w, need_w = conv1x1s2_wgrad(x, w, grad_out, backend), False
+    if need_x and ctx_dgrad:
+        grad_x, need_x = conv1x1s2_bwd_data(grad_out, w, x.shape, None, backend), False
+    if need_x or need_w:
+        gx, gw = _conv_backward(grad_out, x, w, 2, 0, need_x, need_w)
+        grad_x, grad_w = (gx if need_x else grad_x), (gw if need_w else grad_w)
+    return grad_x, grad_w
+
+
+class _Conv1x1S2(torch.autograd.Function):
+    """`F.conv2d(x, w, None, 2)` of a ResNet shortcut.  Each of the three directions goes to `bbd_conv1x1s2_*` or to
+    MIOpen independently (`fwd`, `dgrad`, `wgrad`); MIOpen's side is the problem it has without this function."""
+
+    @staticmethod
+    def forward(ctx, x, w, fwd, dgrad, wgrad, backend):
+        ctx.dgrad, ctx.wgrad, ctx.backend = dgrad, wgrad, backend
+        ctx.save_for_backward(x, w)
+        return conv1x1s2_fwd(x, w, backend) if fwd else torch.nn.functional.conv2d(x, w, None, 2)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, w = ctx.saved_tensors
+        grad_x, grad_w = _conv1x1s2_backward(ctx.dgrad, ctx.wgrad, ctx.backend, grad_out, x, w, ctx.needs_input_grad[0],
+                                             ctx.needs_input_grad[1])
+        return grad_x, grad_w, None, None, None, None
+
+
+def conv1x1_s2(x, w, backend=None, fwd=None, dgrad=None, wgrad=None):
+    """A ResNet shortcut convolution on `x`, each direction where `conv1x1s2_routed` sends it (`fwd` / `dgrad` / `wgrad`
+    override the table: the tests and tools/conv1x1_bench.py)."""
+    backend = backend or default_backend()
+    fwd = conv1x1s2_routed(x, w, "fwd", backend) if fwd is None else fwd
+    dgrad = conv1x1s2_routed(x, w, "dgrad", backend) if dgrad is None else dgrad
+    wgrad = conv1x1s2_routed(x, w, "wgrad", backend) if wgrad is None else wgrad
+    return _Conv1x1S2.apply(x, w, bool(fwd), bool(dgrad), bool(wgrad), backend)
+
+
+class _BlockEntry(torch.autograd.Function):
+    """The two convolutions that read a down-sampling block's input, `F.conv2d(x, w3, None, 2, 1)` (MIOpen's, both ways)
+    and the shortcut `F.conv2d(x, w1, None, 2)`, as ONE node: the backward adds the shortcut's data gradient into the even
+    positions of the 3x3 convolution's (`bbd_conv1x1s2_bwd_data`, accumulate mode) instead of writing a tensor that is
+    three quarters zeros for autograd to add.  The sum has the composition's values: a two-term fp32 add commutes, and
+    the odd positions had 0.0 added to them."""
+
+    @staticmethod
+    def forward(ctx, x, w3, w1, fwd, wgrad, backend):
+        ctx.wgrad, ctx.backend = wgrad, backend
+        ctx.save_for_backward(x, w3, w1)
+        y3 = torch.nn.functional.conv2d(x, w3, None, 2, 1)
+        y1 = conv1x1s2_fwd(x, w1, backend) if fwd else torch.nn.functional.conv2d(x, w1, None, 2)
+        return y3, y1
+
+    @staticmethod
+    def backward(ctx, g3, g1):
+        x, w3, w1 = ctx.saved_tensors
+        need_x, need_w3, need_w1 = ctx.needs_input_grad[:3]
+        gx = gw3 = gw1 = None
+        if g3 is not None and (need_x or need_w3):
+            gx, gw3 = _conv_backward(g3, x, w3, 2, 1, need_x, need_w3)
+        if g1 is not None:
+            if need_x:
+                if gx is not None and not gx.is_contiguous():
+                    gx = gx.contiguous()
+                gx = conv1x1s2_bwd_data(g1, w1, x.shape, gx, ctx.backend)
+            if need_w1:
+                _, gw1 = _conv1x1s2_backward(False, ctx.wgrad, ctx.backend, g1, x, w1, False, True)
+        return gx, gw3, gw1, None, None, None
+
+
+def block_entry(x, w3, w1, backend=None, fwd=None, wgrad=None):
+    """`(conv2d(x, w3, stride 2, pad 1), conv2d(x, w1, stride 2))` of a down-sampling BasicBlock as one autograd node
+    (`_BlockEntry`); the caller has asked `block_entry_routed(x, w1)`.  The shortcut's forward and weight gradient
+    go where `conv1x1s2_routed` sends them (`fwd` / `wgrad` override the table)."""
+    backend = backend or default_backend()
+    fwd = conv1x1s2_routed(x, w1, "fwd", backend) if fwd is None else fwd
+    wgrad = conv1x1s2_routed(x, w1, "wgrad", backend) if wgrad is None else wgrad
+    return _BlockEntry.apply(x, w3, w1, bool(fwd), bool(wgrad), backend)
+
+
 # ---------------------------------------------------------------------------- disparity head Conv3x3(C -> 1)
 DISP_HEAD_MAX_CHANNELS = 256        # DC_MAXC of csrc/bbd_nn.hip (the weights' shared-memory copy); not in the header
 

@@ -62,8 +62,9 @@ extern "C" {
  * 26 = bbd_up2conv3x3_fwd / _bwd (the decoder's finest up-sample + pad + 3x3 convolution in sub-pixel form);
  * 27 = bbd_sgm_hints (semi-global stereo matching: proxy disparities for --depth_hints);
  * 28 = bbd_depth_metrics_affine (depth evaluation under a per-image least-squares scale and shift);
- * 29 = bbd_stem_conv7s2_fwd / _wgrad (the encoder stems' 7x7 stride-2 convolution and its weight gradient). */
-#define BBD_ABI_VERSION 29
+ * 29 = bbd_stem_conv7s2_fwd / _wgrad (the encoder stems' 7x7 stride-2 convolution and its weight gradient);
+ * 30 = bbd_conv1x1s2_fwd / _bwd_data / _wgrad (the ResNet shortcuts' 1x1 stride-2 convolution, three directions). */
+#define BBD_ABI_VERSION 30
 
 /* Source frames live in separate tensors, one per frame id (inputs[("color", f, 0)],
  * trainer.py:428).  A "slot" indexes a host array of their base pointers. */
@@ -1248,6 +1249,36 @@ int bbd_stem_conv7s2_fwd(const float* x, const float* w, float* out, int N, int 
                          void* stream);
 int bbd_stem_conv7s2_wgrad(const float* x, const float* grad_out, float* grad_w, double* scratch, int scratch_doubles,
                            int N, int C, int K, int H, int W, int normalize, void* stream);
+
+/* The ResNet shortcut convolution - 1x1, stride 2, no padding, no bias, groups 1 (layer{2,3,4}.0.downsample.0 of both
+ * encoders) - in its three directions, straight from the NCHW tensors.  All tensors contiguous fp32;
+ * Ho = (H + 1) / 2, Wo = (W + 1) / 2; any N, H, W >= 1, C and K multiples of 16:
+ *   bbd_conv1x1s2_fwd      : y [N, K, Ho, Wo] = conv2d(x [N, C, H, W], w [K, C, 1, 1], stride 2); one launch; reads the
+ *                            even rows of x only.
+ *   bbd_conv1x1s2_bwd_data : grad_x [N, C, H, W] from grad_y and w; one launch.  accumulate == 0: every element of grad_x
+ *                            is written exactly once, the zeros of odd rows and odd columns included.  accumulate != 0:
+ *                            grad_x holds a tensor already; the gradient is added to its even positions (2 oy, 2 ox) and
+ *                            no other element is read or written.
+ *   bbd_conv1x1s2_wgrad    : grad_w [K, C, 1, 1] (written, not accumulated) = sum over (n, oy, ox) of
+ *                            grad_y[n][k][oy][ox] * x[n][c][2 oy][2 ox]; two launches.  scratch holds
+ *                            bbd_conv1x1s2_wgrad_scratch_doubles(...) doubles (K * C times a count that depends on K and C
+ *                            only, not on N) and scratch_doubles says how many it has; none is read before the call wrote
+ *                            it.
+ * Numerics: v_mfma_f32_16x16x4_f32 is an exact fp32 fma chain; no atomics and nothing zeroed first, so two calls give
+ * equal bits.  Forward: one chain over the C input channels, |y - exact| <= (C + 1) * 2^-24 * sum |w| |x|.  Data
+ * gradient: one chain over the K output channels, |grad_x - exact| <= (K + 1) * 2^-24 * sum |w| |grad_y|; accumulate mode
+ * adds that value to the element in fp32, one more rounding: (K + 2) * 2^-24 * (sum |w| |grad_y| + |grad_x before|).
+ * Weight gradient: every fp32 accumulator takes at most BBD_WGRAD_RUN products and is then added to a double; doubles are
+ * added in a fixed order (per lane, then over the records by the second launch):
+ * |grad_w - exact| <= (BBD_WGRAD_RUN + 1) * 2^-24 * sum |grad_y| |x|.
+ * The two host-side queries are declared in include/bbd_conv1x1.h.  A shape bbd_conv1x1s2_supported refuses - C or K not
+ * a multiple of 16, N, H or W below 1, a tensor of 2^31 elements or more - a NULL pointer or a scratch that is too small
+ * return BBD_E_BADARG and launch nothing. */
+int bbd_conv1x1s2_fwd(const float* x, const float* w, float* y, int N, int C, int K, int H, int W, void* stream);
+int bbd_conv1x1s2_bwd_data(const float* grad_y, const float* w, float* grad_x, int N, int C, int K, int H, int W,
+                           int accumulate, void* stream);
+int bbd_conv1x1s2_wgrad(const float* x, const float* grad_y, float* grad_w, double* scratch, int scratch_doubles, int N,
+                        int C, int K, int H, int W, void* stream);
 
 /* ---- MonoViT encoder (BASELINE configs[4]): depth-wise convolution on token-layout activations ----------
  * The position encodings of the reference's MPViT (networksvit/mpvit.py:240-330: ConvPosEnc, ConvRelPosEnc)
